@@ -5,10 +5,13 @@ One step = one frame through every GPU stage, inputs resident in HBM:
   MC (inter prediction of every block from 2 resident reference pictures) -> itx (residual
   add) -> deblock (A -> D, 64x64 tiles: column edges then row edges) -> CDEF (D -> C) -> loop restoration
   (C + D -> O, the reference picture). Descriptors follow SURVEY.md §8(d) config 3.
-Film grain (output-only, configs[3] = 8K10) is timed separately on an 8K10 frame and
-reported under "film_grain_8k10"; the intra path (configs[1], 1080p8: intra prediction +
-itx residual per block in one persistent launch) under "intra_1080p8". Neither is part of
-the headline step.
+A plain run sets up, warms up, times `--steps` steps, writes the last step's pictures if
+`--dump-outputs DIR` is given, and prints the result line. Everything else is behind `--full`:
+the per-kernel event timing and roofline figures, the oracle check of the output, two frames in
+flight, film grain (output-only, configs[3] = 8K10; timed separately on an 8K10 frame and
+reported under "film_grain_8k10"), the intra path (configs[1], 1080p8: intra prediction +
+itx residual per block in one persistent launch; "intra_1080p8"), the end-to-end, output-side
+and real-stream figures and the CPU baseline. None of them is part of the headline step.
 
 `python bench.py` runs 1 GPU. Under torch.distributed.run every rank drives its own GPU on
 its own independent stream (replicas; no data-path collective; "scaling": "weak"); the
@@ -190,6 +193,10 @@ class Pipeline:
             devs += [self.mc.blocks, self.mc.masks]
         return [(d, self.coef0.cpu().pin_memory() if d is self.coefs[0] else d.cpu().pin_memory()) for d in devs]
 
+    def outputs(self, prefix=""):
+        """What a caller of step() receives: the visible pixels of the reference picture O."""
+        return picture_arrays(self.O, prefix)
+
     def output_digest(self):
         """sha256 over the visible pixels of the reference picture O (every plane)."""
         import hashlib
@@ -211,6 +218,31 @@ def oracle_digest(fr):
         hh = fr["h"] if p == 0 else (fr["h"] + ss_ver) >> ss_ver
         h.update(np.ascontiguousarray(a[:hh, :w]).tobytes())
     return h.hexdigest()
+
+
+DUMP_BUDGET = 60 * 10 ** 6  # bytes of float32 that --dump-outputs writes at most (64 MB with headers to spare)
+
+
+def dump_outputs(path, arrays, budget=DUMP_BUDGET):
+    """--dump-outputs: every array of {name: ndarray} as <path>/<name>.npy in float32 (exact for
+    pixels of up to 16 bits). Whole arrays while they fit `budget` together; otherwise the same
+    fraction of each, flattened, at sorted positions drawn by a generator seeded with the
+    array's name and size (the same positions in every run and every build)."""
+    import zlib
+    os.makedirs(path, exist_ok=True)
+    total = sum(a.size * 4 for a in arrays.values())
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if total > budget:
+            keep = max(1, int(a.size * (budget / total)))
+            rng = np.random.default_rng([zlib.crc32(name.encode()), a.size])
+            a = a.reshape(-1)[np.sort(rng.choice(a.size, size=keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
+def picture_arrays(pic, prefix=""):
+    """{name: visible pixels} of every plane of a Frame, the arrays dump_outputs takes."""
+    return {f"{prefix}{'yuv'[p]}": pic.plane_np(p) for p in range(len(pic.planes))}
 
 
 def broadcast_config(cfg, world):
@@ -687,8 +719,15 @@ def single_stream(args, world, rank, local):
     for _ in range(max(1, args.warmup)):
         ps.run(specs)
     torch.cuda.synchronize()
-    elapsed = timed_region(lambda: ps.run(specs), args.steps, torch.cuda.synchronize, world, "cuda")
+    last = {}
+    elapsed = timed_region(lambda: last.update(ps.run(specs)), args.steps, torch.cuda.synchronize, world, "cuda")
     frames = args.steps * len(specs)
+    if args.dump_outputs:
+        # the pictures this rank reconstructed in the last timed step, by decode index
+        arrays = {}
+        for idx, pic in sorted(last.items()):
+            arrays.update(picture_arrays(pic, f"frame{idx:03d}_"))
+        dump_outputs(args.dump_outputs, arrays, DUMP_BUDGET // world)
     if rank == 0:
         print(json.dumps({
             "metric": "decoded Mpixels/s (one 4K 10-bit 4:2:0 stream, frames pipelined over the GPUs)",
@@ -784,6 +823,13 @@ def parse_args(argv):
     ap.add_argument("--frame", default=f"{W}x{H}", help=argparse.SUPPRESS)   # tests: a small frame
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: per-kernel event timing and roofline figures, the oracle check of "
+                         "the output, two frames in flight, 8K10 film grain, 1080p8 intra, end-to-end / output / "
+                         "real-stream figures and the CPU baseline (each has its own --no-... switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the pictures the last timed step produced as DIR/<name>.npy "
+                         "(float32; a fixed seeded sample of every array when they exceed 60 MB together)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-fg", action="store_true", help="skip the separate 8K10 film-grain measurement")
     ap.add_argument("--no-intra", action="store_true", help="skip the separate 1080p8 intra measurement")
@@ -857,22 +903,24 @@ def replicas(args, world, rank, local, hw):
     hw.sync()
     pipe.refill()
 
-    # per-kernel timing pass (HIP events on the launch stream), then the clean timed pass
-    ev = {}
-    for _ in range(max(5, args.steps // 5)):
-        pipe.step(stream, ev)
-    hw.sync()
-    pipe.refill()
-    hw.sync()
-    stage_ms = {k: float(np.mean([a.elapsed_time(b) for a, b in v])) for k, v in ev.items()}
+    # --full: per-kernel timing pass (HIP events on the launch stream), then the clean timed pass
+    stage_ms = {}
+    if args.full:
+        ev = {}
+        for _ in range(max(5, args.steps // 5)):
+            pipe.step(stream, ev)
+        hw.sync()
+        pipe.refill()
+        hw.sync()
+        stage_ms = {k: float(np.mean([a.elapsed_time(b) for a, b in v])) for k, v in ev.items()}
 
     # frames in flight: independent frames on their own streams (and contexts: a context's
     # scratch belongs to one stream), the first on the default stream. The headline runs
     # --inflight frames per step (default 1: every launch has the GPU to itself, so the event
-    # durations above are the kernels' own); with --two-in-flight, two frames in flight (rav1d's
-    # frame threads) are measured beside it (not in the default run: its concurrent launches
+    # durations above are the kernels' own); with --full and --two-in-flight, two frames in flight
+    # (rav1d's frame threads) are measured beside it (not in the plain run: its concurrent launches
     # would mix into a profiler's per-kernel averages of this command).
-    n_pipes = max(args.inflight, 2 if args.two_in_flight else 1)
+    n_pipes = max(args.inflight, 2 if args.full and args.two_in_flight else 1)
     pipes = [(pipe, stream)]
     for _ in range(n_pipes - 1):
         pk = hw.pipeline(hw.context(local), fr, ring)
@@ -917,12 +965,61 @@ def replicas(args, world, rank, local, hw):
             step_fn()
         hw.sync()
     elapsed = timed_region(step_fn, args.steps, hw.sync, world, hw.device)
+    if args.dump_outputs:
+        # what the last timed step left in every in-flight frame's reference picture
+        arrays = {}
+        for k, (pk, _) in enumerate(pipes[:args.inflight]):
+            arrays.update(pk.outputs((f"rank{rank}_" if world > 1 else "") + (f"frame{k}_" if args.inflight > 1 else "")))
+        dump_outputs(args.dump_outputs, arrays, DUMP_BUDGET // world)
+    ranks, want, elapsed2, concurrent_ok = None, None, None, None
+    if args.full:
+        ranks, want, elapsed2, concurrent_ok = checks(args, world, rank, hw, fr, pipes, step_k, elapsed)
+    frames = args.steps * world * args.inflight
+    value = frames * fw * fh / elapsed / 1e6
+    if rank == 0:
+        out = {
+            "metric": "decoded Mpixels/s (4K 10-bit 4:2:0, post-entropy reconstruction DSP)",
+            "value": round(value, 2),
+            "unit": "Mpixels/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+            "fps": round(frames / elapsed, 2),
+            "frames_in_flight": args.inflight,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "u16",
+            "data": "synthetic (seeded inter-frame descriptors per SURVEY.md §8d config 3: uniformly random MVs, the "
+                    "worst case for reference reuse); the reference's real 4K / 1080p inter and intra streams are "
+                    "under real_streams (--full)",
+            "frame": f"{fw}x{fh}",
+            "headline": "kernel-only: every input resident in HBM, one fresh coefficient arena per step; the "
+                        "PCIe-inclusive figure (upload + kernels + output copy) is end_to_end_4k10 (--full)",
+            "arena_ring": ring,
+            "config": {"workload": f"4K10 4:2:0 {fw}x{fh} inter frame: mc (2 refs, 30% compound) + itx residual "
+                                   f"+ deblock + cdef + lr",
+                       "parallelism": f"replicas{world} (one independent stream per GPU)"},
+            "mv_field": args.mv,
+            "full": args.full,
+        }
+        if args.full:
+            out.update(full_report(args, world, fw, fh, ctx, stream, fr, pipe, stage_ms, ranks, want, elapsed2,
+                                   concurrent_ok))
+        print(json.dumps(out), flush=True)
+
+
+def checks(args, world, rank, hw, fr, pipes, step_k, elapsed):
+    """--full, after the timed region: the oracle check of the timed picture, two frames in
+    flight, and every rank's result gathered. Returns (ranks, want, elapsed2, concurrent_ok)."""
+    pipe, stream = pipes[0]
     # the picture the last timed step left (every timed step consumed a fresh arena, so it is
     # the frame the oracle computes); checked below with the rank's oracle digest
     timed_digest = pipe.output_digest()
     want = hw.oracle_digest(fr) if not args.no_verify else None
     elapsed2, concurrent_ok = None, None
-    if args.inflight == 1 and n_pipes >= 2:
+    if args.inflight == 1 and len(pipes) >= 2:
         for pk, _ in pipes[:2]:
             pk.refill()
         hw.sync()
@@ -949,76 +1046,53 @@ def replicas(args, world, rank, local, hw):
             verified = verified and pk.output_digest() == digest
     ranks = gather_results({"rank": rank, "frames": args.steps * args.inflight, "ns": int(elapsed * 1e9),
                             "sha256": digest, "verified": verified}, world)
+    return ranks, want, elapsed2, concurrent_ok
 
+
+def full_report(args, world, fw, fh, ctx, stream, fr, pipe, stage_ms, ranks, want, elapsed2, concurrent_ok):
+    """--full: the entries of the result line beside the headline's own (rank 0)."""
     dom = max(stage_ms, key=stage_ms.get)
     achieved = pipe.algo[dom] / (stage_ms[dom] / 1e3) / 1e9
-    frames = args.steps * world * args.inflight
-    value = frames * fw * fh / elapsed / 1e6
-    if rank == 0:
-        out = {
-            "metric": "decoded Mpixels/s (4K 10-bit 4:2:0, post-entropy reconstruction DSP)",
-            "value": round(value, 2),
-            "unit": "Mpixels/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-            "fps": round(frames / elapsed, 2),
-            "frames_in_flight": args.inflight,
-            "two_frames_in_flight": None if elapsed2 is None else {
-                "value": round(2 * args.steps * world * fw * fh / elapsed2 / 1e6, 2),
-                "ms_per_step": round(elapsed2 / args.steps * 1e3, 4),
-                "outputs_match_sequential": concurrent_ok,
-                "note": "two independent frames per step on two HIP streams / contexts (frame threading); "
-                        "the pictures of the concurrent steps compared with a step run alone"},
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "u16",
-            "data": "synthetic (seeded inter-frame descriptors per SURVEY.md §8d config 3: uniformly random MVs, the "
-                    "worst case for reference reuse); the reference's real 4K / 1080p inter and intra streams are "
-                    "under real_streams",
-            "frame": f"{fw}x{fh}",
-            "headline": "kernel-only: every input resident in HBM, one fresh coefficient arena per step; the "
-                        "PCIe-inclusive figure (upload + kernels + output copy) is end_to_end_4k10",
-            "arena_ring": ring,
-            "config": {"workload": f"4K10 4:2:0 {fw}x{fh} inter frame: mc (2 refs, 30% compound) + itx residual "
-                                   f"+ deblock + cdef + lr",
-                       "parallelism": f"replicas{world} (one independent stream per GPU)"},
-            "verified": all(r["verified"] for r in ranks) if not args.no_verify else None,
-            "per_rank": ranks,
-            "stage_ms": {k: round(v, 4) for k, v in stage_ms.items()},
-            "stage_gbs": {k: round(pipe.algo[k] / (stage_ms[k] / 1e3) / 1e9, 1) for k in stage_ms if k in pipe.algo},
-            # per launch: algorithmic bytes / mean launch duration (the stage's events span its
-            # launches_per_step launches); traffic = PMC HBM bytes per launch (r01_traffic.json)
-            "roofline": {"kernel": pipe.kernels[dom], "stage": dom, "bound": "hbm",
-                         "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 4),
-                         "traffic": per_launch(pmc_traffic(dom), pipe.launches[dom]),
-                         "algo_bytes_per_launch": pipe.algo[dom] // pipe.launches[dom],
-                         "launch_us": round(stage_ms[dom] * 1e3 / pipe.launches[dom], 2),
-                         "launches_per_step": pipe.launches[dom]},
-            # the same figures for every stage's kernel (north_star sets >= 0.5 on itx and deblock)
-            "stage_roofline": {k: {"kernel": pipe.kernels[k], "achieved": round(pipe.algo[k] / (stage_ms[k] / 1e3) / 1e9, 1),
-                                   "frac": round(pipe.algo[k] / (stage_ms[k] / 1e3) / 1e9 / HBM_PEAK_GBS, 4),
-                                   "traffic": per_launch(pmc_traffic(k), pipe.launches[k]),
-                                   "algo_bytes_per_launch": pipe.algo[k] // pipe.launches[k],
-                                   "launch_us": round(stage_ms[k] * 1e3 / pipe.launches[k], 2)}
-                               for k in stage_ms if k in pipe.algo},
-            "mv_field": args.mv,
-        }
-        if world == 1 and not args.no_fg:
-            out["film_grain_8k10"] = film_grain_8k(ctx, stream)
-        if world == 1 and not args.no_intra:
-            out["intra_1080p8"] = intra_1080p8(ctx)
-        if world == 1 and not args.no_extra:
-            out["end_to_end_4k10"] = end_to_end_4k10(fr, want)
-            out["mc_coherent_4k10"] = mc_coherent(ctx, stream)
-            out["output_4k10"] = output_4k10(ctx, stream)
-            out["real_streams"] = real_streams(ctx)
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(fr)
-        print(json.dumps(out), flush=True)
+    out = {
+        "two_frames_in_flight": None if elapsed2 is None else {
+            "value": round(2 * args.steps * world * fw * fh / elapsed2 / 1e6, 2),
+            "ms_per_step": round(elapsed2 / args.steps * 1e3, 4),
+            "outputs_match_sequential": concurrent_ok,
+            "note": "two independent frames per step on two HIP streams / contexts (frame threading); "
+                    "the pictures of the concurrent steps compared with a step run alone"},
+        "verified": all(r["verified"] for r in ranks) if not args.no_verify else None,
+        "per_rank": ranks,
+        "stage_ms": {k: round(v, 4) for k, v in stage_ms.items()},
+        "stage_gbs": {k: round(pipe.algo[k] / (stage_ms[k] / 1e3) / 1e9, 1) for k in stage_ms if k in pipe.algo},
+        # per launch: algorithmic bytes / mean launch duration (the stage's events span its
+        # launches_per_step launches); traffic = PMC HBM bytes per launch (r01_traffic.json)
+        "roofline": {"kernel": pipe.kernels[dom], "stage": dom, "bound": "hbm",
+                     "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                     "frac": round(achieved / HBM_PEAK_GBS, 4),
+                     "traffic": per_launch(pmc_traffic(dom), pipe.launches[dom]),
+                     "algo_bytes_per_launch": pipe.algo[dom] // pipe.launches[dom],
+                     "launch_us": round(stage_ms[dom] * 1e3 / pipe.launches[dom], 2),
+                     "launches_per_step": pipe.launches[dom]},
+        # the same figures for every stage's kernel (north_star sets >= 0.5 on itx and deblock)
+        "stage_roofline": {k: {"kernel": pipe.kernels[k], "achieved": round(pipe.algo[k] / (stage_ms[k] / 1e3) / 1e9, 1),
+                               "frac": round(pipe.algo[k] / (stage_ms[k] / 1e3) / 1e9 / HBM_PEAK_GBS, 4),
+                               "traffic": per_launch(pmc_traffic(k), pipe.launches[k]),
+                               "algo_bytes_per_launch": pipe.algo[k] // pipe.launches[k],
+                               "launch_us": round(stage_ms[k] * 1e3 / pipe.launches[k], 2)}
+                           for k in stage_ms if k in pipe.algo},
+    }
+    if world == 1 and not args.no_fg:
+        out["film_grain_8k10"] = film_grain_8k(ctx, stream)
+    if world == 1 and not args.no_intra:
+        out["intra_1080p8"] = intra_1080p8(ctx)
+    if world == 1 and not args.no_extra:
+        out["end_to_end_4k10"] = end_to_end_4k10(fr, want)
+        out["mc_coherent_4k10"] = mc_coherent(ctx, stream)
+        out["output_4k10"] = output_4k10(ctx, stream)
+        out["real_streams"] = real_streams(ctx)
+    if world == 1 and not args.no_cpu_baseline:
+        out["cpu_baseline"] = cpu_baseline(fr)
+    return out
 
 
 if __name__ == "__main__":

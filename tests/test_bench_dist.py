@@ -162,7 +162,8 @@ def _main_worker(rank, world, port, q):
     import bench
     buf = io.StringIO()
     with contextlib.redirect_stdout(buf):
-        rc = bench.main(["--gpus", str(world), "--steps", "2", "--warmup", "1", "--frame", "128x64"], hw=_CpuHw())
+        rc = bench.main(["--gpus", str(world), "--steps", "2", "--warmup", "1", "--frame", "128x64", "--full"],
+                        hw=_CpuHw())
     q.put((rank, rc, buf.getvalue()))
 
 

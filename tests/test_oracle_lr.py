@@ -1,7 +1,8 @@
 """CPU checks of the loop-restoration oracle (oracle/lr.c)."""
 import ctypes
+import json
 import os
-import re
+import sys
 
 import numpy as np
 import pytest
@@ -11,19 +12,26 @@ from tests import oracle_lib
 from tests.oracle_lib import load_oracle
 from tests.test_oracle_lf import pad_planes
 
-REF_TABLES = "/root/reference/src/tables.c"
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-@pytest.mark.skipif(not os.path.exists(REF_TABLES), reason="reference not mounted")
+def ref_table_digest(name):
+    """Length and SHA-256 of the reference's dav1d_<name> (src/tables.c), recorded in
+    tests/golden/ref_tables.json by tools/gen_tables.py --digests."""
+    return json.load(open(os.path.join(ROOT, "tests", "golden", "ref_tables.json")))[name]
+
+
+def table_digest(vals):
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import gen_tables
+    return gen_tables.digest(vals)
+
+
 def test_sgr_x_by_x_formula_matches_reference_table():
-    txt = open(REF_TABLES).read()
-    body = txt[txt.index("dav1d_sgr_x_by_x[256]"):]
-    body = body[body.index("{") + 1: body.index("}")]
-    ref = [int(v) for v in re.findall(r"\d+", body)]
     o = load_oracle()
     o.oracle_sgr_x_by_x.restype = ctypes.POINTER(ctypes.c_uint8)
     ours = o.oracle_sgr_x_by_x()
-    assert [ours[i] for i in range(256)] == ref
+    assert table_digest([ours[i] for i in range(256)]) == ref_table_digest("sgr_x_by_x")
 
 
 def planes_for(w, h, bpc, layout, rng):

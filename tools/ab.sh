@@ -18,7 +18,7 @@ done
 for rep in 1 2; do
   for v in "$@"; do
     if [ $v = base ]; then L=$R/rav1d_amd/librav1d_amd.so; else L=$R/rav1d_amd/librav1d_amd_$v.so; fi
-    MI_LIB=$L timeout -k 10 200 python $R/bench.py --steps 50 --no-cpu-baseline --no-fg > $OUT/bench_${v}_$rep.json || { echo "$v bench failed"; exit 1; }
+    MI_LIB=$L timeout -k 10 200 python $R/bench.py --full --steps 50 --no-cpu-baseline --no-fg > $OUT/bench_${v}_$rep.json || { echo "$v bench failed"; exit 1; }
     python -c "import json,sys;d=json.load(open(sys.argv[1]));print(sys.argv[2], d['value'], d['stage_ms'])" $OUT/bench_${v}_$rep.json $v
   done
 done

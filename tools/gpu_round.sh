@@ -13,7 +13,7 @@ timeout -k 10 600 python -u -m pytest $R/tests -m gpu -x -q --timeout 150 --time
 rc=$?; tail -2 $OUT/pytest_gpu_$TAG.log; stop $rc pytest
 timeout -k 10 150 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke_$TAG.log 2>&1
 rc=$?; tail -1 $OUT/smoke_$TAG.log; stop $rc smoke
-timeout -k 10 420 python -u $R/bench.py --steps 20 --warmup 5 > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err
+timeout -k 10 420 python -u $R/bench.py --full --steps 20 --warmup 5 > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err
 rc=$?; tail -c 400 $OUT/bench_$TAG.err; stop $rc bench
 if [ -n "$EXTRA" ]; then
   bash -c "$EXTRA"
