@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define MI_AV1DEC_ABI_VERSION 2
+#define MI_AV1DEC_ABI_VERSION 3
 
 /* The pass-2 work of one decoded frame. All pointers stay valid until the next
  * mi_dec_next() / mi_dec_destroy() on the same decoder. */
@@ -104,7 +104,11 @@ typedef struct MiDecFrame {
 
 /* One decoder event: a frame to reconstruct into picture `pic_id` (frame != NULL; its inter
  * prediction reads pictures ref_pic[]), and/or a picture to output (show_pic >= 0, with film
- * grain when fg_present). Pictures listed in release[] are no longer referenced. */
+ * grain when fg_present). Pictures listed in release[] are no longer referenced.
+ * show_pic need not be pic_id: a show_existing_frame names an earlier picture, and with
+ * mi_dec_set_all_layers(d, 0) a shown frame's event has show_pic -1 (or the picture held back
+ * before it) and the frame's picture is shown by a later event, or by none. A picture held
+ * back is in no release[] before the event that shows or drops it. */
 typedef struct MiDecEvent {
     const MiDecFrame *frame;
     int32_t pic_id;
@@ -115,6 +119,10 @@ typedef struct MiDecEvent {
     const int32_t *release;
     int32_t n_release;
     int32_t mtrx_identity;   /* seq_hdr.mtrx == DAV1D_MC_IDENTITY (the grain's chroma clip, fg_apply.rs) */
+    /* (ABI 3) the OBU extension's layer ids of the shown picture's frame (show_pic >= 0; else
+     * of `frame`), and whether that frame was the first decoded of its temporal unit */
+    int32_t temporal_id, spatial_id;
+    int32_t new_temporal_unit;
 } MiDecEvent;
 
 /* ---- device execution of a decoded frame (these two live in librav1d_amd.so) ----
@@ -196,6 +204,39 @@ int  mi_dec_set_threads(MiDec *d, int n);
 #define MI_INLOOPFILTER_RESTORATION (1 << 3)
 #define MI_INLOOPFILTER_ALL (MI_INLOOPFILTER_DEBLOCK | MI_INLOOPFILTER_CDEF | MI_INLOOPFILTER_RESTORATION)
 int  mi_dec_set_inloop_filters(MiDec *d, int flags);
+/* The remaining decode controls of Dav1dSettings (src/lib.rs:199-219), each set before the
+ * first mi_dec_send, each 0 or -EINVAL.
+ *
+ * operating_point (0..31, the CLI's --oppoint): at every sequence header the operating point
+ * decoded is `op`, or 0 when the sequence has no more than `op` of them; OBUs whose extension
+ * names a temporal or spatial layer outside its idc are dropped (sequence headers and temporal
+ * delimiters excepted, obu.rs:2195-2205). Default 0.
+ *
+ * all_layers (--alllayers; default 1): with 0 and an operating point of more than one spatial
+ * layer, only the highest spatial layer's picture of each temporal unit is shown; every frame
+ * is still decoded, the lower layers being the references of the upper (output_picture_ready,
+ * src/lib.rs:412-438). A shown picture waits in a one-picture cache: when the next one arrives
+ * the cached picture is shown if it is of the operating point's highest spatial layer or the
+ * new picture starts a temporal unit, and dropped otherwise. mi_dec_drain() at the end of the
+ * input queues the last picture held back; it does nothing otherwise, with any settings.
+ *
+ * decode_frame_type (--decodeframetype): frames left out by type are neither reconstructed nor
+ * shown (obu.rs:2493-2515, 2629-2648): REFERENCE leaves out inter, switch and intra-only frames
+ * that refresh no slot, INTRA every inter and switch frame, KEY everything but key frames. The
+ * slots such a frame refreshes keep its header and no picture: a later show_existing_frame of
+ * one, or an inter frame predicting from one, is -EINVAL. Default ALL.
+ *
+ * frame_size_limit (--sizelimit): a frame header whose upscaled width * height exceeds `pixels`
+ * makes mi_dec_send return -ERANGE (obu.rs:2342-2352). 0 (default): no limit. */
+#define MI_DECODEFRAMETYPE_ALL 0
+#define MI_DECODEFRAMETYPE_REFERENCE 1
+#define MI_DECODEFRAMETYPE_INTRA 2
+#define MI_DECODEFRAMETYPE_KEY 3
+int  mi_dec_set_operating_point(MiDec *d, int op);
+int  mi_dec_set_all_layers(MiDec *d, int on);
+int  mi_dec_set_decode_frame_type(MiDec *d, int type);
+int  mi_dec_set_frame_size_limit(MiDec *d, unsigned pixels);
+int  mi_dec_drain(MiDec *d);
 /* Feed one temporal unit (any whole number of OBUs). */
 int  mi_dec_send(MiDec *d, const uint8_t *data, size_t size);
 /* Next event: 1 and *ev filled, 0 when none is pending, or -errno. */

@@ -51,7 +51,9 @@ class MiDecEvent(ctypes.Structure):
                 ("ref_pic", ctypes.c_int32 * 7), ("show_pic", ctypes.c_int32),
                 ("fg_present", ctypes.c_int32), ("fg", MiFilmGrainData),
                 ("release", ctypes.POINTER(ctypes.c_int32)), ("n_release", ctypes.c_int32),
-                ("mtrx_identity", ctypes.c_int32)]
+                ("mtrx_identity", ctypes.c_int32),
+                ("temporal_id", ctypes.c_int32), ("spatial_id", ctypes.c_int32),
+                ("new_temporal_unit", ctypes.c_int32)]
 
 
 def build_dec():
@@ -71,6 +73,11 @@ def dec_lib():
         d.mi_dec_next.argtypes = [ctypes.c_void_p, ctypes.POINTER(MiDecEvent)]
         d.mi_dec_set_threads.argtypes = [ctypes.c_void_p, ctypes.c_int]
         d.mi_dec_set_inloop_filters.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        d.mi_dec_set_operating_point.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        d.mi_dec_set_all_layers.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        d.mi_dec_set_decode_frame_type.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        d.mi_dec_set_frame_size_limit.argtypes = [ctypes.c_void_p, ctypes.c_uint]
+        d.mi_dec_drain.argtypes = [ctypes.c_void_p]
         d.mi_dec_error.argtypes = [ctypes.c_void_p]
         d.mi_dec_error.restype = ctypes.c_char_p
         _dec = d
@@ -178,15 +185,30 @@ INLOOPFILTER_ALL = INLOOPFILTER_DEBLOCK | INLOOPFILTER_CDEF | INLOOPFILTER_RESTO
 # the CLI's --inloopfilters values (inloop_filters_tbl, tools/dav1d_cli_parse.rs:479-530)
 INLOOPFILTER_NAMES = {"none": 0, "deblock": 2, "nodeblock": 12, "cdef": 4, "nocdef": 10,
                       "restoration": 8, "norestoration": 6, "all": 14}
+# Dav1dSettings.decode_frame_type (include/dav1d/dav1d.rs:50-70) under the CLI's
+# --decodeframetype names
+DECODEFRAMETYPE_NAMES = {"all": 0, "reference": 1, "intra": 2, "key": 3}
+
+
+class DecoderError(RuntimeError):
+    """A negative return of the front-end; code is the -errno."""
+
+    def __init__(self, what, code, why=""):
+        super().__init__(f"{what}: {code} ({why})")
+        self.code = code
 
 
 class Av1Decoder:
-    """One stream. send() one temporal unit, then drain events()."""
+    """One stream. send() one temporal unit, then drain events(); drain() after the last."""
 
-    def __init__(self, threads=1, inloop_filters=INLOOPFILTER_ALL):
+    def __init__(self, threads=1, inloop_filters=INLOOPFILTER_ALL, operating_point=0, all_layers=True,
+                 decode_frame_type="all", frame_size_limit=0):
         """threads > 1: intra frames are decoded on that many worker threads (mi_dec_set_threads);
         send a few temporal units ahead of draining events() to overlap them. inloop_filters:
-        Dav1dSettings.inloop_filters (an int of INLOOPFILTER_* bits or a CLI name)."""
+        Dav1dSettings.inloop_filters (an int of INLOOPFILTER_* bits or a CLI name).
+        operating_point, all_layers, decode_frame_type (an int or a DECODEFRAMETYPE_NAMES key) and
+        frame_size_limit: the Dav1dSettings fields of those names (include/mi_av1dec.h); a value
+        the front-end rejects raises ValueError."""
         self.lib = dec_lib()
         self.h = ctypes.c_void_p()
         r = self.lib.mi_dec_create(ctypes.byref(self.h))
@@ -200,6 +222,21 @@ class Av1Decoder:
             r = self.lib.mi_dec_set_inloop_filters(self.h, int(inloop_filters))
             if r:
                 raise ValueError(f"mi_dec_set_inloop_filters({inloop_filters}): {r}")
+        if isinstance(decode_frame_type, str):
+            if decode_frame_type not in DECODEFRAMETYPE_NAMES:
+                raise ValueError(f"decode_frame_type {decode_frame_type!r}")
+            decode_frame_type = DECODEFRAMETYPE_NAMES[decode_frame_type]
+        for name, v, default in (("operating_point", int(operating_point), 0),
+                                 ("all_layers", int(bool(all_layers)), 1),
+                                 ("decode_frame_type", int(decode_frame_type), 0),
+                                 ("frame_size_limit", int(frame_size_limit), 0)):
+            if v == default:
+                continue
+            if name == "frame_size_limit" and not 0 <= v < 1 << 32:
+                raise ValueError(f"frame_size_limit {v}")
+            r = getattr(self.lib, "mi_dec_set_" + name)(self.h, v)
+            if r:
+                raise ValueError(f"mi_dec_set_{name}({v}): {r}")
 
     def __del__(self):
         if getattr(self, "h", None):
@@ -212,7 +249,14 @@ class Av1Decoder:
     def send(self, data):
         r = self.lib.mi_dec_send(self.h, data, len(data))
         if r < 0:
-            raise RuntimeError(f"mi_dec_send: {r} ({self.error()})")
+            raise DecoderError("mi_dec_send", r, self.error())
+
+    def drain(self):
+        """The end of the input (mi_dec_drain): the picture all_layers=False holds back becomes
+        a last event. A no-op otherwise."""
+        r = self.lib.mi_dec_drain(self.h)
+        if r < 0:
+            raise DecoderError("mi_dec_drain", r, self.error())
 
     def events(self):
         """Yield MiDecEvent structs; each is valid only until the next one is requested."""
@@ -220,18 +264,20 @@ class Av1Decoder:
         while True:
             r = self.lib.mi_dec_next(self.h, ctypes.byref(ev))
             if r < 0:
-                raise RuntimeError(f"mi_dec_next: {r} ({self.error()})")
+                raise DecoderError("mi_dec_next", r, self.error())
             if r == 0:
                 return
             yield ev
 
 
-def stream_events(data, threads=1, lookahead=None, inloop_filters=INLOOPFILTER_ALL):
+def stream_events(data, threads=1, lookahead=None, inloop_filters=INLOOPFILTER_ALL, operating_point=0,
+                  all_layers=True, decode_frame_type="all", frame_size_limit=0):
     """Decoder events of a stream (IVF, Annex B or section 5) in decode order. With threads > 1 the front-end keeps
     `lookahead` (default 2 * threads) temporal units ahead of the events handed out, so that
     frames decode on the worker threads while the caller consumes earlier ones. Each event is
-    valid until the next one is requested."""
-    dec = Av1Decoder(threads, inloop_filters)
+    valid until the next one is requested. The other settings are Av1Decoder's; the decoder is
+    drained after the last unit."""
+    dec = Av1Decoder(threads, inloop_filters, operating_point, all_layers, decode_frame_type, frame_size_limit)
     la = 0 if threads <= 1 else (lookahead if lookahead is not None else 2 * threads)
     # (threads > 1 with lookahead 0: one temporal unit at a time, its frame's tiles in parallel)
     sent = 0
@@ -247,4 +293,5 @@ def stream_events(data, threads=1, lookahead=None, inloop_filters=INLOOPFILTER_A
                 yield ev
         else:
             yield from gen
+    dec.drain()
     yield from dec.events()

@@ -38,6 +38,41 @@ int mi_dec_set_inloop_filters(MiDec *d, int flags) {
     return 0;
 }
 
+int mi_dec_set_operating_point(MiDec *d, int op) {
+    if (!d || op < 0 || op > 31) return -EINVAL;
+    d->dec.operating_point = op;
+    return 0;
+}
+
+int mi_dec_set_all_layers(MiDec *d, int on) {
+    if (!d) return -EINVAL;
+    d->dec.all_layers = on != 0;
+    return 0;
+}
+
+int mi_dec_set_decode_frame_type(MiDec *d, int type) {
+    if (!d || type < MI_DECODEFRAMETYPE_ALL || type > MI_DECODEFRAMETYPE_KEY) return -EINVAL;
+    d->dec.decode_frame_type = type;
+    return 0;
+}
+
+int mi_dec_set_frame_size_limit(MiDec *d, unsigned pixels) {
+    if (!d) return -EINVAL;
+    d->dec.frame_size_limit = pixels;
+    return 0;
+}
+
+int mi_dec_drain(MiDec *d) {
+    if (!d) return -EINVAL;
+    try {
+        d->dec.drain();
+    } catch (const std::bad_alloc &) {
+        d->dec.error = "out of memory";
+        return -ENOMEM;
+    }
+    return 0;
+}
+
 const char *mi_dec_error(const MiDec *d) { return d ? d->dec.error.c_str() : "null decoder"; }
 
 int mi_dec_send(MiDec *d, const uint8_t *data, size_t size) {
@@ -78,6 +113,9 @@ int mi_dec_next(MiDec *d, MiDecEvent *ev) {
     ev->fg_present = e.fg_present;
     ev->fg = e.fg;
     ev->mtrx_identity = e.mtrx_identity;
+    ev->temporal_id = e.temporal_id;
+    ev->spatial_id = e.spatial_id;
+    ev->new_temporal_unit = e.new_tu;
     d->release.assign(e.release.begin(), e.release.end());
     ev->release = d->release.data();
     ev->n_release = (int32_t)d->release.size();

@@ -32,6 +32,7 @@ struct RefSlot {
     int refpoc[7];
     int bw, bh;   // 4x4-unit frame size the segmap / mvs belong to
     int showable;
+    int new_tu = 0;   // the frame was the first its temporal unit decoded (PICTURE_FLAG_NEW_TEMPORAL_UNIT)
 };
 
 // One entry of the decoder's output queue: a frame to reconstruct (work != null) and/or a
@@ -46,6 +47,17 @@ struct DecEvent {
     int fg_present = 0;
     int mtrx_identity = 0;           // the grain's chroma clip (seq_hdr.mtrx == MC_IDENTITY)
     std::vector<int> release;        // pictures no slot references any more
+    // layer ids of the shown picture's frame (show_pic >= 0; else of `work`'s frame), and whether
+    // that frame was the first its temporal unit decoded
+    int temporal_id = 0, spatial_id = 0, new_tu = 0;
+};
+
+// A picture on its way out (c.out / c.cache of the reference: src/lib.rs output_picture_ready).
+struct ShownPic {
+    int pic = -1;
+    MiFilmGrainData fg{};
+    int fg_present = 0, mtrx_identity = 0;
+    int temporal_id = 0, spatial_id = 0, new_tu = 0;
 };
 
 class Decoder {
@@ -60,6 +72,13 @@ public:
     // parses on (an inter frame's job waits for the jobs of its references), each frame's
     // tiles on up to n threads; events still come out in decode order. 1 (default): synchronous.
     void set_threads(int n);
+    // Dav1dSettings (src/lib.rs:199-219), set before the first send():
+    int operating_point = 0;          // index into the sequence header's operating points
+    bool all_layers = true;           // false: only the highest spatial layer of a temporal unit is shown
+    int decode_frame_type = 0;        // DAV1D_DECODEFRAMETYPE_*: 0 all, 1 reference, 2 intra, 3 key
+    unsigned frame_size_limit = 0;    // upscaled width * height a frame may have (0: any)
+    // End of input: queues the picture all_layers == false holds back (a no-op otherwise).
+    void drain();
     ~Decoder();
     std::string error;
 
@@ -73,6 +92,9 @@ private:
                      const std::shared_ptr<const Cdf> &cdf, const std::shared_ptr<const std::vector<uint8_t>> &segmap,
                      const std::shared_ptr<const std::vector<TmvBlock>> &mvs, const int *refpoc, int bw, int bh);
     void release_unused(DecEvent &ev, const int *old_ids);
+    void skip_frame();
+    int show(DecEvent &ev, const ShownPic &p);
+    void end_hold(DecEvent &ev, int id);
     void resolve(RefSlot &r);
     void resolve_all();
 
@@ -88,6 +110,10 @@ private:
     int n_tiles_ = 0;
     int next_pic_ = 0;
     std::deque<DecEvent> out_;
+    int op_idc_ = 0;            // idc of the selected operating point (0: every OBU belongs to it)
+    int max_spatial_id_ = 0;    // its highest spatial layer
+    int new_tu_ = 0;            // a temporal delimiter was seen since the last frame decoded
+    ShownPic cache_;            // the shown picture held back (all_layers == false); pic < 0: none
 };
 
 // What a frame decoding on a worker makes available to the frames that reference it before it

@@ -735,9 +735,9 @@ int Decoder::parse_obu(const uint8_t *data, size_t size, size_t *used) {
     *used = hdr_bytes + len;
     const uint8_t *obu = data + hdr_bytes;
 
-    if (type != 1 && type != 2 && has_ext && seq_ && seq_->op_idc[0]) {
-        const int idc = seq_->op_idc[0];
-        if (!((idc >> temporal_id) & 1) || !((idc >> (spatial_id + 8)) & 1)) return 0;
+    // an OBU outside the selected operating point's layers is dropped (obu.rs:2195-2205)
+    if (type != 1 && type != 2 && has_ext && op_idc_) {
+        if (!((op_idc_ >> temporal_id) & 1) || !((op_idc_ >> (spatial_id + 8)) & 1)) return 0;
     }
     switch (type) {
     case 1: {   // sequence header
@@ -749,6 +749,11 @@ int Decoder::parse_obu(const uint8_t *data, size_t size, size_t *used) {
             error = "bad sequence header";
             return r;
         }
+        // the operating point this sequence is decoded at (obu.rs:2265-2276): its idc selects
+        // the OBUs above and gives the highest spatial layer
+        op_idc_ = s->op_idc[operating_point < s->num_op ? operating_point : 0];
+        max_spatial_id_ = 0;
+        for (int m = op_idc_ >> 8; m > 1; m >>= 1) max_spatial_id_++;
         if (seq_ && memcmp(s.get(), seq_.get(), sizeof(SeqHdr))) {
             // a new sequence: forget everything decoded under the old one
             int old_ids[8];
@@ -781,17 +786,37 @@ int Decoder::parse_obu(const uint8_t *data, size_t size, size_t *used) {
         }
         tiles_.clear();
         n_tiles_ = 0;
+        if (frame_size_limit &&
+            (int64_t)frame_hdr_->width[1] * frame_hdr_->height > (int64_t)frame_size_limit) {
+            frame_hdr_.reset();
+            error = "frame size exceeds the limit";
+            return -ERANGE;
+        }
         if (frame_hdr_->show_existing_frame) {
             if (type == 6) return -EINVAL;
             const int idx = frame_hdr_->existing_frame_idx;
+            if (!refs_[idx].hdr) return -EINVAL;
+            // Dav1dSettings.decode_frame_type: a frame of a type left out is not shown either
+            // (obu.rs:2493-2515)
+            const int ft = refs_[idx].hdr->frame_type;
+            if ((ft == FRAME_INTER || ft == FRAME_SWITCH) ? decode_frame_type > 1
+                                                         : ft == FRAME_INTRA && decode_frame_type > 2) {
+                frame_hdr_.reset();
+                break;
+            }
             resolve(refs_[idx]);
             const RefSlot &rs = refs_[idx];
-            if (!rs.hdr || rs.pic_id < 0) return -EINVAL;
+            if (rs.pic_id < 0) return -EINVAL;   // (the slot of a skipped frame: a header, no picture)
             DecEvent ev;
-            ev.show_pic = rs.pic_id;
-            ev.fg_present = rs.hdr->fg.present;
-            ev.fg = rs.hdr->fg.data;
-            ev.mtrx_identity = seq_->mtrx == 0;
+            ShownPic sp;
+            sp.pic = rs.pic_id;
+            sp.fg_present = rs.hdr->fg.present;
+            sp.fg = rs.hdr->fg.data;
+            sp.mtrx_identity = seq_->mtrx == 0;
+            sp.temporal_id = rs.hdr->temporal_id;
+            sp.spatial_id = rs.hdr->spatial_id;
+            sp.new_tu = rs.new_tu;
+            const int ended = show(ev, sp);
             if (rs.hdr->frame_type == FRAME_KEY) {
                 // a shown key frame refreshes every slot (obu.rs show_existing_frame)
                 int old_ids[8];
@@ -804,7 +829,8 @@ int Decoder::parse_obu(const uint8_t *data, size_t size, size_t *used) {
                 }
                 release_unused(ev, old_ids);
             }
-            out_.push_back(std::move(ev));
+            end_hold(ev, ended);
+            if (ev.show_pic >= 0 || !ev.release.empty()) out_.push_back(std::move(ev));
             frame_hdr_.reset();
             break;
         }
@@ -852,11 +878,22 @@ int Decoder::parse_obu(const uint8_t *data, size_t size, size_t *used) {
         n_tiles_ += end - start + 1;
         break;
     }
-    default:   // temporal delimiter, metadata, padding, tile list: nothing for the pixels
+    case 2:   // temporal delimiter: the next frame decoded starts a temporal unit
+        new_tu_ = 1;
+        break;
+    default:   // metadata, padding, tile list: nothing for the pixels
         break;
     }
     if (frame_hdr_ && !frame_hdr_->show_existing_frame &&
         n_tiles_ == frame_hdr_->tiling.cols * frame_hdr_->tiling.rows && !tiles_.empty()) {
+        // Dav1dSettings.decode_frame_type: frames left out by type (obu.rs:2629-2648)
+        const int ft = frame_hdr_->frame_type, dft = decode_frame_type;
+        const bool unreferenced = dft == 1 && !frame_hdr_->refresh_frame_flags;
+        if ((ft == FRAME_INTER || ft == FRAME_SWITCH) ? dft > 1 || unreferenced
+                                                     : ft == FRAME_INTRA && (dft > 2 || unreferenced)) {
+            skip_frame();
+            return 0;
+        }
         const int r = submit_frame();
         frame_hdr_.reset();
         tiles_.clear();
@@ -866,10 +903,81 @@ int Decoder::parse_obu(const uint8_t *data, size_t size, size_t *used) {
     return 0;
 }
 
+// A frame left out by decode_frame_type: the slots it refreshes keep its header and lose their
+// picture (obu.rs:2137-2151 skip); a later frame that needs the picture is a bitstream error.
+void Decoder::skip_frame() {
+    int old_ids[8];
+    for (int i = 0; i < 8; i++) old_ids[i] = refs_[i].pic_id;
+    auto hdr_c = std::shared_ptr<const FrameHdr>(frame_hdr_);
+    for (int i = 0; i < 8; i++)
+        if (frame_hdr_->refresh_frame_flags & (1 << i)) {
+            refs_[i].pic_id = -1;
+            refs_[i].hdr = hdr_c;
+        }
+    frame_hdr_.reset();
+    tiles_.clear();
+    n_tiles_ = 0;
+    DecEvent ev;
+    release_unused(ev, old_ids);
+    if (!ev.release.empty()) out_.push_back(std::move(ev));
+}
+
+// `ev` shows picture `s`
+static void put(DecEvent &ev, const ShownPic &s) {
+    ev.show_pic = s.pic;
+    ev.fg_present = s.fg_present;
+    ev.fg = s.fg;
+    ev.mtrx_identity = s.mtrx_identity;
+    ev.temporal_id = s.temporal_id;
+    ev.spatial_id = s.spatial_id;
+    ev.new_tu = s.new_tu;
+}
+
+// A shown picture on its way out (src/lib.rs:391-438 output_picture_ready / output_image, one
+// call per picture that reaches c.out). With every layer wanted, or an operating point of one
+// spatial layer, `ev` shows it. Otherwise it is held back in a one-picture cache, and the
+// picture held so far is shown by `ev` if it belongs to the operating point's highest spatial
+// layer or `p` starts a new temporal unit, and dropped if not. Returns the picture that left
+// the cache (-1: none): end_hold() after the event's slot updates. The highest spatial layer is
+// compared as the id itself, as dav1d's C does; rav1d keeps it as a bool, the same rule for up
+// to two spatial layers. Both give the recorded MD5 of every reference test, vq_suite 020's
+// four spatial layers included.
+int Decoder::show(DecEvent &ev, const ShownPic &p) {
+    if (all_layers || !max_spatial_id_) {
+        put(ev, p);
+        return -1;
+    }
+    const int ended = cache_.pic;
+    if (ended >= 0 && (cache_.spatial_id == max_spatial_id_ || p.new_tu)) put(ev, cache_);
+    cache_ = p;
+    return ended;
+}
+
+// Picture `id` has left the cache (shown or dropped): released here if no slot kept it (while
+// held back it was left out of every release list).
+void Decoder::end_hold(DecEvent &ev, int id) {
+    if (id < 0 || id == cache_.pic) return;
+    for (int j = 0; j < 8; j++)
+        if (refs_[j].pic_id == id) return;
+    for (int v : ev.release)
+        if (v == id) return;
+    ev.release.push_back(id);
+}
+
+void Decoder::drain() {
+    if (cache_.pic < 0) return;
+    const ShownPic c = cache_;
+    cache_ = ShownPic();
+    DecEvent ev;
+    if (!all_layers && max_spatial_id_) put(ev, c);   // (else a sequence of one layer took over: dropped)
+    end_hold(ev, c.pic);
+    if (ev.show_pic >= 0 || !ev.release.empty()) out_.push_back(std::move(ev));
+}
+
 void Decoder::release_unused(DecEvent &ev, const int *old_ids) {
     for (int i = 0; i < 8; i++) {
         const int id = old_ids[i];
-        if (id < 0) continue;
+        if (id < 0 || id == cache_.pic) continue;   // (a picture held back stays: end_hold)
         bool live = false;
         for (int j = 0; j < 8; j++) live |= refs_[j].pic_id == id;
         bool listed = false;
@@ -1152,11 +1260,23 @@ int Decoder::submit_frame() {
     ev.pic_id = next_pic_++;
     if (!intra)
         for (int i = 0; i < 7; i++) ev.ref_pic[i] = in.refs[i]->pic_id;
+    // the frame takes the temporal unit's start flag, shown or not (picture.rs: p.flags)
+    const int new_tu = new_tu_;
+    new_tu_ = 0;
+    ev.temporal_id = h.temporal_id;
+    ev.spatial_id = h.spatial_id;
+    ev.new_tu = new_tu;
+    int ended = -1;
     if (h.show_frame) {
-        ev.show_pic = ev.pic_id;
-        ev.fg_present = h.fg.present;
-        ev.fg = h.fg.data;
-        ev.mtrx_identity = s.mtrx == 0;
+        ShownPic sp;
+        sp.pic = ev.pic_id;
+        sp.fg_present = h.fg.present;
+        sp.fg = h.fg.data;
+        sp.mtrx_identity = s.mtrx == 0;
+        sp.temporal_id = h.temporal_id;
+        sp.spatial_id = h.spatial_id;
+        sp.new_tu = new_tu;
+        ended = show(ev, sp);
     }
     // reference slots (decode.rs submit_frame: refresh_frame_flags)
     std::shared_ptr<const Cdf> slot_cdf;
@@ -1191,10 +1311,13 @@ int Decoder::submit_frame() {
         rs.bw = bw;
         rs.bh = bh;
         rs.showable = h.showable_frame;
+        rs.new_tu = new_tu;
     }
     release_unused(ev, old_ids);
-    // the new picture itself is dead if no slot holds it and it is not shown
-    bool live = false;
+    end_hold(ev, ended);
+    // the new picture itself is dead if no slot holds it (and it is not held back to be shown
+    // by a later event)
+    bool live = ev.pic_id == cache_.pic;
     for (int j = 0; j < 8; j++) live |= refs_[j].pic_id == ev.pic_id;
     if (!live) ev.release.push_back(ev.pic_id);
     out_.push_back(std::move(ev));

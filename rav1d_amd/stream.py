@@ -55,15 +55,19 @@ def _refs(pics, ev, key=lambda p: p):
     return out
 
 
-def decode_ivf(ctx, data, stream=None, sync_each=True, inloop_filters=14, threads=1):
+def decode_ivf(ctx, data, stream=None, sync_each=True, inloop_filters=14, threads=1, operating_point=0,
+               all_layers=True, decode_frame_type="all", frame_size_limit=0):
     """Decode a stream (IVF, Annex B or section 5) on the device; yields the shown pictures (Frame, device planes) in
     output order. With sync_each, every frame is checked with mi_frame_end before it is shown.
     inloop_filters: Dav1dSettings.inloop_filters (rav1d_amd.av1dec.INLOOPFILTER_*). threads > 1: the
-    front-end's frame and tile threads (mi_dec_set_threads)."""
-    dec = Av1Decoder(threads, inloop_filters=inloop_filters)
+    front-end's frame and tile threads (mi_dec_set_threads). operating_point, all_layers,
+    decode_frame_type, frame_size_limit: the Dav1dSettings fields of those names
+    (rav1d_amd.av1dec.Av1Decoder). A picture the front-end holds back (all_layers=False) stays in
+    `pics` until the event that shows or drops it: the front-end lists it in no release[] before."""
+    dec = Av1Decoder(threads, inloop_filters, operating_point, all_layers, decode_frame_type, frame_size_limit)
     pics = {}
-    for tu in stream_units(data):
-        dec.send(tu)
+
+    def consume():
         for ev in dec.events():
             if ev.frame:
                 pics[ev.pic_id] = run_frame(ctx, ev.frame.contents, stream, _refs(pics, ev))
@@ -73,6 +77,12 @@ def decode_ivf(ctx, data, stream=None, sync_each=True, inloop_filters=14, thread
                 yield pics[ev.show_pic].output()
             for i in range(ev.n_release):
                 pics.pop(ev.release[i], None)
+
+    for tu in stream_units(data):
+        dec.send(tu)
+        yield from consume()
+    dec.drain()
+    yield from consume()
     frame_end(ctx, stream)
 
 
@@ -93,7 +103,8 @@ def _lanes(ctx, stream, n):
 
 
 def decode_to_muxer(ctx, data, muxer, stream=None, apply_grain=True, pipelined=True, threads=8, in_flight=2,
-                    inloop_filters=14, stats=None):
+                    inloop_filters=14, stats=None, operating_point=0, all_layers=True, decode_frame_type="all",
+                    frame_size_limit=0):
     """Decode an IVF stream on the device and write every shown picture through `muxer`
     (rav1d_amd.output.Muxer): the picture leaves HBM once, via mi_output_picture into pinned
     host memory, with film grain applied in that same pass when the frame carries grain and
@@ -110,6 +121,11 @@ def decode_to_muxer(ctx, data, muxer, stream=None, apply_grain=True, pipelined=T
     Device failures of any frame are reported by the mi_frame_end calls at the end of the
     stream. Without pipelined: one frame at a time, each checked by mi_frame_end before it is
     shown, the front-end one temporal unit at a time (its tiles still on `threads` threads).
+
+    operating_point, all_layers, decode_frame_type, frame_size_limit: the Dav1dSettings fields of
+    those names (rav1d_amd.av1dec.Av1Decoder). A picture held back by all_layers=False is shown by
+    a later event than its frame's: it is copied out on the lane that reconstructed it, and stays
+    in the pools until that event (the front-end releases it no earlier).
 
     stats: a dict to receive the per-stage breakdown: host time waiting for the
     front-end's events (front_end_ms), host time inside mi_frame_run (run_host_ms), the device
@@ -153,7 +169,9 @@ def decode_to_muxer(ctx, data, muxer, stream=None, apply_grain=True, pipelined=T
     slot = 0
     # (without pipelined the front-end still decodes each frame's tiles on `threads` threads,
     # but no temporal unit ahead of the one the device is given)
-    events = iter(stream_events(data, threads, lookahead=None if pipelined else 0, inloop_filters=inloop_filters))
+    events = iter(stream_events(data, threads, lookahead=None if pipelined else 0, inloop_filters=inloop_filters,
+                                operating_point=operating_point, all_layers=all_layers,
+                                decode_frame_type=decode_frame_type, frame_size_limit=frame_size_limit))
     while True:
         t = clock()
         ev = next(events, None)

@@ -2,10 +2,13 @@
 -> product md5 muxer), on the GPU box.
 
     python tools/gpu_sweep.py prepare DIR     # container: copy the vectors + expected MD5s into DIR
+    python tools/gpu_sweep.py prepare DIR --explicit   # only the explicit test() entries
     python tools/gpu_sweep.py run DIR OUT     # GPU box: decode them all, one JSON line per vector
 
 DIR is scratch (gitignored): the vectors are the reference's test data
-(tests/dav1d-test-data/**/meson.build) and travel to the box only for this sweep.
+(tests/dav1d-test-data/**/meson.build) and travel to the box only for this sweep. The explicit
+test() entries are in the table with their arguments (--oppoint, --alllayers, --decodeframetype,
+--filmgrain) and run with those settings.
 """
 import json
 import os
@@ -17,18 +20,19 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def prepare(d):
-    from tools.make_stream_fixtures import GRAIN
-    from tools.scan_vectors import vectors
+def prepare(d, explicit_only=False):
+    from tools.scan_vectors import entry_name, explicit_tests, vectors
     os.makedirs(d, exist_ok=True)
     base = "/root/reference/tests/dav1d-test-data"
-    table = [(n, os.path.relpath(p, base), m, 0) for n, p, m in vectors()]
-    table += [(n, rel, m, 1) for n, rel, m in GRAIN]
+    table = [] if explicit_only else [(n, os.path.relpath(p, base), m, None) for n, p, m in vectors()]
+    table += [(entry_name(n, a), os.path.relpath(p, base), m, a) for n, p, m, a in explicit_tests()]
     out = []
-    for name, rel, md5, fg in table:
+    for name, rel, md5, args in table:
         dst = rel.replace("/", "__")
         shutil.copyfile(os.path.join(base, rel), os.path.join(d, dst))
-        out.append({"name": name, "file": dst, "md5": md5, "filmgrain": fg})
+        out.append({"name": name, "file": dst, "md5": md5, "filmgrain": args["filmgrain"] if args else 0})
+        if args:
+            out[-1]["args"] = args
     json.dump(out, open(os.path.join(d, "vectors.json"), "w"))
     print(len(out), "vectors")
 
@@ -46,7 +50,10 @@ def run(d, out_path):
             m = Muxer("md5")
             t = time.time()
             try:
-                n = decode_to_muxer(ctx, data, m, apply_grain=bool(v["filmgrain"]))
+                a = v.get("args") or {}
+                n = decode_to_muxer(ctx, data, m, apply_grain=bool(v["filmgrain"]), operating_point=a.get("oppoint", 0),
+                                    all_layers=bool(a.get("alllayers", 1)),
+                                    decode_frame_type=a.get("decodeframetype", "all"))
                 got = m.digest()
                 st = "ok" if got == v["md5"] else "MISMATCH"
             except Exception as e:  # noqa: BLE001 - record and continue
@@ -55,7 +62,8 @@ def run(d, out_path):
             ok += st == "ok"
             bad += st == "MISMATCH"
             err += st == "error"
-            f.write(json.dumps({"name": v["name"], "file": v["file"], "status": st, "frames": n, "md5": got,
+            f.write(json.dumps({"name": v["name"], "file": v["file"], "args": v.get("args"), "status": st, "frames": n,
+                                "md5": got,
                                 "s": round(time.time() - t, 3)}) + "\n")
             f.flush()
             print(st, v["name"], n, flush=True)
@@ -64,6 +72,6 @@ def run(d, out_path):
 
 if __name__ == "__main__":
     if sys.argv[1] == "prepare":
-        prepare(sys.argv[2])
+        prepare(sys.argv[2], "--explicit" in sys.argv[3:])
     else:
         run(sys.argv[2], sys.argv[3])

@@ -1,6 +1,8 @@
 """Copy the reference's MD5 test vectors that the front-end decodes into tests/golden/streams/
 (data only: the IVF inputs and the expected MD5 from tests/dav1d-test-data/**/meson.build), and
-write tests/golden/streams/vectors.json. Run in the container (reads /root/reference)."""
+write tests/golden/streams/vectors.json; then the explicit test() entries of the sframe, svc and
+vq_suite lists, with the decoder settings they name, into tests/golden/settings/. Run in the
+container (reads /root/reference)."""
 import json
 import os
 import shutil
@@ -8,7 +10,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from tools.scan_vectors import vectors  # noqa: E402
+from tools.scan_vectors import DATA, entry_name, explicit_tests, vectors  # noqa: E402
 
 # (meson name, path under tests/dav1d-test-data) of the vectors pinned so far
 PINNED = [
@@ -80,6 +82,44 @@ def driver_suite(by_path):
     return [(by_path[rel][0], rel, by_path[rel][1]) for rel in sorted(by_path)]
 
 
+# committed files stay below this size: a longer stream is stored as consecutive parts
+PART = 768 << 10
+SETTINGS_DIRS = ("8-bit/sframe", "8-bit/svc", "8-bit/vq_suite")
+
+
+def write_settings(streams_table):
+    """tests/golden/settings/: the explicit test() entries of SETTINGS_DIRS (--oppoint,
+    --alllayers, --decodeframetype, --filmgrain) as vectors.json, and the streams among them
+    that tests/golden/streams/ does not hold already (those are named by a relative path)."""
+    base = DATA
+    out = os.path.join(ROOT, "tests", "golden", "settings")
+    os.makedirs(out, exist_ok=True)
+    in_streams = {t["source"].split(" ")[0]: t["file"] for t in streams_table}
+    table = []
+    for name, path, md5, args in explicit_tests():
+        rel = os.path.relpath(path, base)
+        if os.path.dirname(rel) not in SETTINGS_DIRS:
+            continue
+        entry = {"name": entry_name(name.replace("Syntax_AV1_mainb8ss420_432x240", "vq").replace("_vq_aom_ctest_4.2", "")
+                                    .replace("av1-1-b8-22-", ""), args),
+                 "md5": md5, "args": args, "source": f"tests/dav1d-test-data/{rel}"}
+        if entry["source"] in in_streams:
+            entry["file"] = "../streams/" + in_streams[entry["source"]]
+        else:
+            entry["file"] = dst = rel.replace("/", "__")
+            data = open(path, "rb").read()
+            if len(data) > PART:
+                entry["parts"] = [f"{dst}.part{i}" for i in range((len(data) + PART - 1) // PART)]
+                for i, pn in enumerate(entry["parts"]):
+                    open(os.path.join(out, pn), "wb").write(data[i * PART:(i + 1) * PART])
+            else:
+                shutil.copyfile(path, os.path.join(out, dst))
+        table.append(entry)
+    assert len({t["name"] for t in table}) == len(table)
+    json.dump(table, open(os.path.join(out, "vectors.json"), "w"), indent=1)
+    print(len(table), "settings vectors")
+
+
 if __name__ == "__main__":
     out = os.path.join(ROOT, "tests", "golden", "streams")
     os.makedirs(out, exist_ok=True)
@@ -111,3 +151,4 @@ if __name__ == "__main__":
                       "source": f"tests/dav1d-test-data/{rel} --filmgrain 1"})
     json.dump(table, open(os.path.join(out, "vectors.json"), "w"), indent=1)
     print(len(table), "vectors")
+    write_settings(table)
