@@ -132,7 +132,11 @@ typedef struct MiDecEvent {
  * restored ((cdef, deblocked) -> restored). Stages the frame header switches off are skipped,
  * not copied: *final receives the index (0 recon .. 3 restored) of the picture holding the
  * frame's reference-quality output (the picture rav1d leaves in f.sr_cur after
- * filter_sbrow: recon.rs:4019-4211). */
+ * filter_sbrow: recon.rs:4019-4211).
+ * `recon` is an intermediate, not an output: for an inter frame without intra blocks whose
+ * deblocking is on and runs out of place (recon != deblocked), the DC-only residual blocks'
+ * constants are added while deblocking (MI_ITX_DC_DEFER, mi_av1dsp.h), so `recon` lacks them
+ * after the call; `deblocked` and every later picture are complete. */
 typedef struct MiFramePictures {
     MiPicture recon, deblocked, cdef, restored;
     MiPicture refs[7];    /* the reference pictures of an inter frame (MiDecEvent.ref_pic order,

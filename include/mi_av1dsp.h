@@ -63,7 +63,10 @@ typedef struct MiPicture {
  * non-DC block of more than 16 coefficients packed. With MI_TX_I16 as well (10/12-bit arenas
  * only) the corner's coefficients are int16: coefficient (x, y) is
  * ((const int16_t *)(arena + coef_off))[y*CW + x] and the block spans CW*CH/2 int32 entries
- * (the front-end sets it when every coefficient of the corner fits). Other flag bits: 0. The
+ * (the front-end sets it when every coefficient of the corner fits). Other flag bits: 0. A
+ * DC-only block (txtp 0 = DCT_DCT, eob < 1) stores its DC alone, at the arena's own width, and
+ * takes no flag: flags != 0 on such a descriptor is illegal (the block is skipped and
+ * mi_ctx_device_status reports -EINVAL; mi_frame_validate rejects the work list). The
  * DSP-table entry points (itxfm_add) keep the reference's dense layout. */
 #define MI_TX_PACKED 0x80u
 #define MI_TX_I16 0x40u
@@ -363,7 +366,13 @@ int mi_itx_frame_banded(MiCtx *ctx, const MiPicture *pic, const MiTxBlock *block
  * pixels; the context records them per 4x4 unit for the next mi_deblock_frame_dc, which adds
  * them to the pixels it stages, so the deblocked picture equals that of the undeferred call
  * while the reconstruction `pic` lacks them (for frames whose reconstruction nothing else reads:
- * no intra block predicts from it). Under stream capture the flag is ignored. */
+ * no intra block predicts from it). Under stream capture the flag is ignored.
+ * A deferral is pending from the return of a deferring call that launched (an empty or failed
+ * call defers nothing) until the next mi_deblock_frame_dc on the context consumes it. It is
+ * cancelled, its DC runs never added, by any later mi_itx_frame / mi_itx_frame_banded /
+ * mi_itx_frame_runs call on the context (with or without the flag, successful or not) and by
+ * mi_deblock_frame and mi_deblock_frame_to. Any coefficient the arena can hold gives the pixel
+ * of the undeferred call (the recorded constant is clamped to +-bitdepth_max first). */
 #define MI_ITX_DC_DEFER 2u
 int mi_itx_frame_runs(MiCtx *ctx, const MiPicture *pic, const MiTxBlock *blocks,
                       const uint32_t band_start[MI_N_RECT_TX_SIZES][MI_ITX_BANDS + 1],
@@ -431,13 +440,17 @@ int mi_deblock_frame(MiCtx *ctx, const MiPicture *pic, const MiLoopFilter *lf, v
  * geometry, src/picture.rs:98-115). One launch of 64x64 plane tiles, each filtering every
  * column edge and then every row edge that reaches it from an LDS copy with a 16/12-px halo;
  * bit-identical to mi_deblock_frame. Planes and strides must be 16-byte aligned. With
- * src == dst it runs mi_deblock_frame (in place). */
+ * src == dst it runs mi_deblock_frame (in place). Both drop a pending MI_ITX_DC_DEFER deferral
+ * of the context without adding it. */
 int mi_deblock_frame_to(MiCtx *ctx, const MiPicture *src, const MiPicture *dst, const MiLoopFilter *lf,
                         void *stream);
 /* mi_deblock_frame_to that adds, while staging, the DC runs the context's last
  * mi_itx_frame_runs(MI_ITX_DC_DEFER) recorded (src never written; with lf->filter_y == 0 the
  * output is src plus the DC). Without a pending deferral it is mi_deblock_frame_to. The picture
- * geometry must be the deferring call's and src != dst (-EINVAL otherwise). */
+ * geometry must be the deferring call's and src != dst (-EINVAL otherwise; the deferral is
+ * consumed all the same). `src`, the reconstruction, keeps lacking the DC runs: only `dst` has
+ * them. While `stream` is capturing, a pending deferral (made outside the capture) is refused
+ * with -EINVAL and stays pending for a later uncaptured call; nothing is enqueued. */
 int mi_deblock_frame_dc(MiCtx *ctx, const MiPicture *src, const MiPicture *dst, const MiLoopFilter *lf,
                         void *stream);
 

@@ -154,6 +154,9 @@ static int itx_frame(MiCtx *ctx, const MiPicture *pic, const MiTxBlock *blocks,
                      const uint32_t *size_start, const uint32_t *band_start, void *coef, unsigned flags,
                      void *stream, const uint32_t *dc_end) {
     if (!ctx || !pic || !size_start) return fail(ctx, -EINVAL);
+    // any itx frame call supersedes a deferral still pending: its DC runs belong to pixels this
+    // call rewrites (only a deferring launch below sets a new one)
+    ctx->dc_pending = 0;
     if (pic->bpc != 8 && pic->bpc != 10 && pic->bpc != 12) return fail(ctx, -EINVAL);
     mi::ItxArgs a;
     memset(&a, 0, sizeof(a));
@@ -180,13 +183,13 @@ static int itx_frame(MiCtx *ctx, const MiPicture *pic, const MiTxBlock *blocks,
     for (int k = 0; k < MI_N_RECT_TX_SIZES; k++)
         if (size_start[k + 1] < size_start[k]) return fail(ctx, -EINVAL);
     const int wg = mi::itx_fill_schedule(a, size_start, band_start, dc_end);
+    bool deferring = false;
     if (flags & MI_ITX_DC_DEFER) {
         // the DC runs go to the context's DC map for the next mi_deblock_frame_dc; under stream
         // capture they are added to the pixels as without the flag (a tag fixed in a graph would
         // let a replay match the map entries of the previous replay)
         hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
         if (hipStreamIsCapturing((hipStream_t)stream, &cap) != hipSuccess) return fail(ctx, -EIO);
-        ctx->dc_pending = 0;
         if (cap == hipStreamCaptureStatusNone) {
             const mi::DcMapGeom g = mi::dc_map_geom(pic->w, pic->h, pic->layout);
             if (g.entries > ctx->dc_map_n) {
@@ -208,12 +211,10 @@ static int itx_frame(MiCtx *ctx, const MiPicture *pic, const MiTxBlock *blocks,
                 a.dc_stride[p] = g.stride[p];
             }
             a.dc_tag = ctx->dc_tag;
-            ctx->dc_pending = ctx->dc_tag;
-            ctx->dc_w = pic->w;
-            ctx->dc_h = pic->h;
-            ctx->dc_layout = pic->layout;
+            deferring = true;
         }
     }
+    // (an empty or refused call defers nothing: no tag is left pending for it)
     if (wg == 0) return 0;
     if (!blocks || !coef) return fail(ctx, -EINVAL);
     // One launch (itx.hip): the large sizes' workgroups first, the small ones fill in around
@@ -221,7 +222,14 @@ static int itx_frame(MiCtx *ctx, const MiPicture *pic, const MiTxBlock *blocks,
     // 56 -> 74 us) than the cross-queue dependency saves.
     hipStream_t s = (hipStream_t)stream;
     const int r = mi::launch_itx_frame(a, wg, pic->bpc, s);
-    return r ? fail(ctx, -EIO) : 0;
+    if (r) return fail(ctx, -EIO);
+    if (deferring) {   // the launch is enqueued: the next mi_deblock_frame_dc owes its DC runs
+        ctx->dc_pending = ctx->dc_tag;
+        ctx->dc_w = pic->w;
+        ctx->dc_h = pic->h;
+        ctx->dc_layout = pic->layout;
+    }
+    return 0;
 }
 
 }  // extern "C"
@@ -526,6 +534,7 @@ int mi_ctx_device_status(MiCtx *ctx, void *stream) {
 
 int mi_deblock_frame(MiCtx *ctx, const MiPicture *pic, const MiLoopFilter *lf, void *stream) {
     if (!ctx || !pic || !lf) return fail(ctx, -EINVAL);
+    ctx->dc_pending = 0;   // a deferral still pending is dropped: only mi_deblock_frame_dc adds it
     if (pic->bpc != 8 && pic->bpc != 10 && pic->bpc != 12) return fail(ctx, -EINVAL);
     if (!lf->filter_y) return 0;   // deblocking off for the frame (recon.rs:4047-4060)
     if (!lf->level || !lf->masks || lf->sb128w <= 0) return fail(ctx, -EINVAL);
@@ -576,6 +585,7 @@ static int deblock_tiles(MiCtx *ctx, const MiPicture *src, const MiPicture *dst,
 
 int mi_deblock_frame_to(MiCtx *ctx, const MiPicture *src, const MiPicture *dst, const MiLoopFilter *lf,
                         void *stream) {
+    if (ctx) ctx->dc_pending = 0;   // as mi_deblock_frame: a pending deferral is dropped
     return deblock_tiles(ctx, src, dst, lf, stream, 0);
 }
 
@@ -583,6 +593,13 @@ int mi_deblock_frame_dc(MiCtx *ctx, const MiPicture *src, const MiPicture *dst, 
                         void *stream) {
     if (!ctx) return -EINVAL;
     const uint32_t tag = ctx->dc_pending;
+    if (tag) {
+        // a tag fixed in a graph would let every replay add whatever entries then carry it: a
+        // deferral made outside the capture is refused here and stays pending
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing((hipStream_t)stream, &cap) != hipSuccess) return fail(ctx, -EIO);
+        if (cap != hipStreamCaptureStatusNone) return fail(ctx, -EINVAL);
+    }
     ctx->dc_pending = 0;
     if (tag && (!src || src->w != ctx->dc_w || src->h != ctx->dc_h || src->layout != ctx->dc_layout))
         return fail(ctx, -EINVAL);

@@ -174,9 +174,12 @@ __host__ __device__ inline TxCoefShape tx_coef_shape(uint8_t flags, int sw, int 
 }
 // a descriptor's flags are legal for a block of sw x sh stored coefficients at arena offset
 // coef_off (a packed corner starts on a 4-coefficient boundary: its rows are vector loads;
-// int16 corners only in the int32 arenas of 10/12-bit frames)
-__host__ __device__ inline bool tx_flags_ok(uint8_t flags, int sw, int sh, uint32_t coef_off, bool hbd) {
+// int16 corners only in the int32 arenas of 10/12-bit frames). A DC-only block (DCT_DCT,
+// eob < 1) takes no flag: its one stored coefficient is read at the arena's own width
+__host__ __device__ inline bool tx_flags_ok(uint8_t flags, int sw, int sh, uint32_t coef_off, bool hbd, int txtp,
+                                            int eob) {
     if (!flags) return true;
+    if (txtp == 0 && eob < 1) return false;
     return (flags & MI_TX_PACKED) && (!(flags & MI_TX_I16) || hbd) && (int)MI_TX_PACKED_CW(flags) <= sw &&
            (int)MI_TX_PACKED_CH(flags) <= sh && (coef_off & 3) == 0;
 }

@@ -175,10 +175,11 @@ thread_local const char *g_why = nullptr;
 
 // the coefficients a transform block reads from the arena: a DC-only block (DCT_DCT, eob < 1)
 // its DC alone (the front-end stores only that), a packed block its CW x CH corner
-// (MI_TX_PACKED; half as many int32 entries with MI_TX_I16), any other the min(w,32) x min(h,32) run; illegal flags: more than any arena
+// (MI_TX_PACKED; half as many int32 entries with MI_TX_I16), any other the min(w,32) x min(h,32) run; illegal flags
+// (any flag on a DC-only block among them): more than any arena
 size_t coef_span(const mi::TxDim &d, int txtp, int eob, uint8_t flags, uint32_t coef_off, bool hbd) {
     const int sw = std::min(d.w, 32), sh = std::min(d.h, 32);
-    if (!mi::tx_flags_ok(flags, sw, sh, coef_off, hbd)) return SIZE_MAX / 2;
+    if (!mi::tx_flags_ok(flags, sw, sh, coef_off, hbd, txtp, eob)) return SIZE_MAX / 2;
     if (txtp == 0 && eob < 1) return 1;
     const mi::TxCoefShape cs = mi::tx_coef_shape(flags, sw, sh);
     return (size_t)cs.cw * cs.ch / (flags & MI_TX_I16 ? 2 : 1);
@@ -726,6 +727,13 @@ int frame_run(MiCtx *ctx, const MiDecFrame *f, const MiFramePictures *pics, int 
     if (ctx->tm_on) ctx->tm_strips_ms += pl.strips_ms;
     // the intra queue: the front-end's (MiDecFrame.q_*, planned in its frame job) or this plan's
     const bool inter = mi_plan::inter_present(f) || f->n_inter_tx;
+    // DC-only residuals deferred into the deblocking pass (MI_ITX_DC_DEFER) when nothing reads
+    // the reconstruction itself: no intra block predicts from it, and deblocking runs out of
+    // place (its output is what CDEF, LR and the reference picture read). pics->recon then lacks
+    // the DC runs. The one condition decides both the deferring residual call and the deblock
+    // call that adds the runs (mi_deblock_frame_dc); every other frame deblocks through
+    // mi_deblock_frame_to, which drops a deferral a failed earlier frame may have left pending.
+    const bool dc_defer = f->n_inter_tx && n == 0 && f->filter_y && pics->recon.data[0] != pics->deblocked.data[0];
     const bool have_q = f->q_intra != nullptr;
     const bool granules = have_q ? f->q_granules != 0 : pl.iq.granules;
     const MiIntraBlock *q_blocks = have_q ? f->q_intra : pl.iq.blocks.data();
@@ -823,10 +831,7 @@ int frame_run(MiCtx *ctx, const MiDecFrame *f, const MiFramePictures *pics, int 
                                                        (int)lap_s[k].size(), tmp, stream)))
                 return r;
         }
-        // DC-only residuals deferred into the deblocking pass (MI_ITX_DC_DEFER) when nothing
-        // reads the reconstruction itself: no intra block predicts from it, and deblocking runs
-        // out of place (its output is what CDEF, LR and the reference picture read)
-        const bool dc_defer = n == 0 && f->filter_y && pics->recon.data[0] != pics->deblocked.data[0];
+        // (dc_defer: the DC runs go to step 2's mi_deblock_frame_dc instead of the pixels)
         if (f->n_inter_tx &&
             (r = mi_itx_frame_runs(ctx, &cur, (const MiTxBlock *)D(20), itx_bs, pl.itx_dc, D(4),
                                    MI_ITX_KEEP_COEFS | (dc_defer ? MI_ITX_DC_DEFER : 0u), stream)))
@@ -886,8 +891,10 @@ int frame_run(MiCtx *ctx, const MiDecFrame *f, const MiFramePictures *pics, int 
         lf.filter_uv = f->filter_uv;
         memcpy(lf.lim_e, f->lim_e, 64);
         memcpy(lf.lim_i, f->lim_i, 64);
-        // (adds the DC runs an inter frame's residual call deferred, if any)
-        if ((r = mi_deblock_frame_dc(ctx, cur, &cp[1], &lf, stream))) return r;
+        // (dc_defer: adds the DC runs this frame's residual call deferred)
+        if ((r = dc_defer ? mi_deblock_frame_dc(ctx, cur, &cp[1], &lf, stream)
+                          : mi_deblock_frame_to(ctx, cur, &cp[1], &lf, stream)))
+            return r;
         cur = &cp[1];
         idx = 1;
     }

@@ -6,7 +6,8 @@
 //
 // Mapping. Blocks arrive grouped by tx size (inside a size, DC-only blocks first and then by
 // position keeps control flow wave-uniform and lets neighbouring blocks of a workgroup share
-// pixel lines). One launch per frame; a 256-lane workgroup takes BPW blocks of one size:
+// pixel lines). One launch per frame; a one-wave (kItxThreads = 64) workgroup takes BPW blocks
+// of one size:
 //   1. every lane reads its block descriptor and immediately issues the loads of the
 //      destination pixels it will own in step 4 (4-pixel row chunks, 4/8-byte vector loads),
 //      so they are in flight during the transforms;
@@ -143,7 +144,7 @@ __device__ __forceinline__ void itx_size(const ItxArgs &a, int lwg, Lt *lds) {
             // a descriptor the reference could never issue (wrong size group, a type the
             // size's table slot lacks, a rectangle outside its plane) is skipped and reported
             const bool ok = b.tx == TX && b.txtp < 17 && ((itx_legal_types(TX) >> b.txtp) & 1) &&
-                            tx_flags_ok(b.flags, SW, SH, b.coef_off, sizeof(Cf) == 4) &&
+                            tx_flags_ok(b.flags, SW, SH, b.coef_off, sizeof(Cf) == 4, b.txtp, b.eob) &&
                             b.plane < 3 && b.x + Wd <= sel3(pw3, b.plane) && b.y + Ht <= sel3(ph3, b.plane);
             if (!ok) {
                 valid = false;
@@ -387,9 +388,9 @@ __device__ __forceinline__ void itx_dc(const ItxArgs &a, int lwg, uint8_t *lds) 
             ItxDcRec r{ nullptr, 0, 0 };
             if (t < nb) {
                 const MiTxBlock b = a.blocks[bs + t];
-                // a block the run may not hold (another size, not DC-only, outside its plane) is
-                // skipped and reported, as the transform path does
-                const bool ok = b.tx == TX && b.txtp == 0 && b.eob < 1 && b.plane < 3 &&
+                // a block the run may not hold (another size, not DC-only, flagged, outside its
+                // plane) is skipped and reported, as the transform path does
+                const bool ok = b.tx == TX && b.txtp == 0 && b.eob < 1 && b.flags == 0 && b.plane < 3 &&
                                 b.x + W <= sel3(pw3, b.plane) && b.y + H <= sel3(ph3, b.plane);
                 if (ok) {
                     dcp[rr] = reinterpret_cast<const Cf *>(a.coef) + b.coef_off;
@@ -426,7 +427,10 @@ __device__ __forceinline__ void itx_dc(const ItxArgs &a, int lwg, uint8_t *lds) 
                 dc = (dc * 181 + 128) >> 8;
                 dc = (dc + Rnd) >> Shift;
                 dc = (dc * 181 + 128 + 2048) >> 12;
-                rec[t].dc = dc;
+                // pixel + dc is clipped to [0, bdmax], so a dc clamped to +-bdmax gives the same
+                // pixel: the map's 16-bit field and the deblock tile's packed 16-bit add are then
+                // exact for any coefficient the arena may hold
+                rec[t].dc = clampi(dc, -a.bdmax, a.bdmax);
             }
         }
         __syncthreads();

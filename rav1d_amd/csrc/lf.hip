@@ -756,7 +756,8 @@ __device__ __forceinline__ void lf_commit_pixels_dc(Px *t, const uint4 (&sv)[LfS
             for (int k = 0; k < 4; k++) {
                 if constexpr (sizeof(Px) == 2) {
                     // pixels 2k, 2k + 1 (one unit: (2k) / 4) in packed 16-bit arithmetic: a pixel
-                    // (< 4096) plus a DC (|dc| < 2^15 - 4096 for 12-bit coefficients) fits int16
+                    // (<= bdmax < 4096) plus a map DC (itx_dc clamps it to [-bdmax, bdmax] before
+                    // packing, whatever the coefficient) fits int16
                     const lf_s2 v = __builtin_bit_cast(lf_s2, w[k]) + pk_splat(d[k >> 1]);
                     w[k] = __builtin_bit_cast(uint32_t, pk_clamp(v, pk_splat(0), pk_splat(bdmax)));
                 } else {

@@ -114,6 +114,41 @@ def test_front_end_intra_queue(name):
     assert checked > 0
 
 
+def test_flags_on_dc_only_descriptors_are_rejected():
+    """A DC-only transform block (DCT_DCT, eob < 1) stores its DC alone at the arena's width and
+    takes no flag: MI_TX_PACKED (| MI_TX_I16) on one is rejected in the inter residual list and in
+    the intra work list, while the same flags on the lists' other blocks stay as emitted."""
+    from rav1d_amd import TXBLOCK_DTYPE
+    v = next(x for x in VECTORS if x["name"] == "00000706")
+    data = open(os.path.join(GOLDEN, v["file"]), "rb").read()
+    gen = frames_with_pictures(data)      # kept alive: the frames' arrays belong to the decoder
+    seen = set()
+    for fr, ps, _ in gen:
+        for field, count in (("inter_tx", fr.n_inter_tx), ("intra_tx", fr.n_intra)):
+            if field in seen or not count:
+                continue
+            tx = np.frombuffer(ctypes.string_at(getattr(fr, field), 16 * count), TXBLOCK_DTYPE).copy()
+            dc = np.nonzero((tx["txtp"] == 0) & (tx["eob"] == 0) & (tx["coef_off"] % 4 == 0))[0]
+            if not len(dc):
+                continue
+            assert not tx["flags"][(tx["txtp"] == 0) & (tx["eob"] == 0)].any(), "the front-end emits none"
+            assert validate(fr, ps)[0] == 0
+            for flags in (0xc0, 0x80) if fr.bpc > 8 else (0x80,):
+                bad_tx = tx.copy()
+                bad_tx["flags"][dc[0]] = flags
+                bad = MiDecFrame.from_buffer_copy(fr)
+                setattr(bad, field, bad_tx.ctypes.data)
+                if field == "intra_tx":
+                    bad.q_intra = None      # (mi_frame_run then plans the queue from this list)
+                rc, why = validate(bad, ps)
+                assert rc == -22 and why, (field, hex(flags))
+            seen.add(field)
+        if len(seen) == 2:
+            break
+    assert seen == {"inter_tx", "intra_tx"}
+    del gen
+
+
 def test_malformed_inter_units_are_rejected():
     v = next(x for x in VECTORS if x["name"] == "00000706")
     data = open(os.path.join(GOLDEN, v["file"]), "rb").read()

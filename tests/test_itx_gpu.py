@@ -84,6 +84,24 @@ def test_itx_packed_flags_rejected(gpu):
         assert lib().mi_ctx_device_status(gpu.h, _stream_ptr(None)) == -22
         x, y, p = int(blk["x"][k]), int(blk["y"][k]), int(blk["plane"][k])
         assert np.array_equal(got[p][y:y + 4, x:x + 4], before[p][y:y + 4, x:x + 4])
+    # a DC-only block (DCT_DCT, eob < 1) takes no flag at all: the device reads its one
+    # coefficient at the arena's width, whatever MI_TX_I16 says (a negative int16 DC would read
+    # as 0x0000fffb). On the transform path (plain, banded) and in a DC run alike.
+    for bad, bpc, opts in ((0xc0, 10, {}), (0xc0, 12, dict(banded=True)), (0xc0, 10, dict(runs=True)),
+                           (0x80, 8, dict(runs=True)), (0x01, 10, dict(runs=True))):
+        fr = make_itx_frame(64, 64, bpc=bpc, seed=8)
+        blk = fr["blocks"].copy()
+        k = int(np.nonzero((blk["tx"] == 0) & (blk["txtp"] == 0) & (blk["eob"] < 1) & (blk["coef_off"] % 4 == 0))[0][0])
+        blk["flags"][k] = bad
+        fr["blocks"] = blk
+        fr["coef"] = fr["coef"].copy()
+        fr["coef"][blk["coef_off"][k]] = -500    # a constant of -16 per pixel if it were added
+        before = [p.copy() for p in fr["planes"]]
+        got, _ = run_frame(gpu, fr, **opts)
+        assert lib().mi_ctx_device_status(gpu.h, _stream_ptr(None)) == -22, (bad, bpc, opts)
+        x, y, p = int(blk["x"][k]), int(blk["y"][k]), int(blk["plane"][k])
+        assert np.array_equal(got[p][y:y + 4, x:x + 4], before[p][y:y + 4, x:x + 4])
+        assert lib().mi_ctx_device_status(gpu.h, _stream_ptr(None)) == 0
 
 
 def test_itx_keep_coefs_flag(gpu):
