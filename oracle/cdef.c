@@ -17,6 +17,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include "oracle.h"
+#include "census.h"
 
 static inline int imin(int a, int b) { return a < b ? a : b; }
 static inline int imax(int a, int b) { return a > b ? a : b; }
@@ -86,11 +87,16 @@ void oracle_cdef_filter_block(void *dst_, ptrdiff_t dst_stride, const void *src_
     const int pri_tap = 4 - ((pri >> bdm8) & 1);
     const int pri_shift = pri ? imax(0, damping - ulog2(pri)) : 0;
     const int sec_shift = sec ? damping - ulog2(sec) : 0;
+    CEN_ONLY(const int pri_shift_cut = pri && damping - ulog2(pri) < 0;)
     for (int y = 0; y < h; y++) {
         for (int x = 0; x < w; x++) {
             const int c = tmp[y * TS + x];
             int sum = 0, mx = c;
             unsigned mn = (unsigned)c;
+            CEN_ONLY(int sentinel = 0; int smn = c;)
+/* the sentinel is i16::MIN: as unsigned it never wins the minimum, as int never the maximum */
+#define MINMAX(t) do { mn = umin((unsigned)(t), mn); mx = imax((t), mx); \
+                       CEN_ONLY(sentinel |= (t) == INT16_MIN; smn = imin((t), smn);) } while (0)
             if (pri) {
                 int tap = pri_tap;
                 for (int k = 0; k < 2; k++) {
@@ -99,8 +105,8 @@ void oracle_cdef_filter_block(void *dst_, ptrdiff_t dst_stride, const void *src_
                     sum += tap * constrain(a - c, pri, pri_shift);
                     sum += tap * constrain(b - c, pri, pri_shift);
                     tap = (tap & 3) | 2;
-                    mn = umin((unsigned)a, mn); mx = imax(a, mx);
-                    mn = umin((unsigned)b, mn); mx = imax(b, mx);
+                    MINMAX(a);
+                    MINMAX(b);
                 }
             }
             if (sec) {
@@ -113,15 +119,28 @@ void oracle_cdef_filter_block(void *dst_, ptrdiff_t dst_stride, const void *src_
                     sum += tap * constrain(s1 - c, sec, sec_shift);
                     sum += tap * constrain(s2 - c, sec, sec_shift);
                     sum += tap * constrain(s3 - c, sec, sec_shift);
-                    mn = umin((unsigned)s0, mn); mx = imax(s0, mx);
-                    mn = umin((unsigned)s1, mn); mx = imax(s1, mx);
-                    mn = umin((unsigned)s2, mn); mx = imax(s2, mx);
-                    mn = umin((unsigned)s3, mn); mx = imax(s3, mx);
+                    MINMAX(s0);
+                    MINMAX(s1);
+                    MINMAX(s2);
+                    MINMAX(s3);
                 }
             }
             int v = c + ((sum - (sum < 0) + 8) >> 4);
             /* min/max clamping only when both strengths are active (cdef.rs:700-760) */
-            if (pri && sec) v = iclip(v, (int)mn, mx);
+#undef MINMAX
+            CEN_ONLY(
+                CEN_IF(sentinel, CEN_CDEF_PX_SENTINEL);
+                CEN_IF(pri_shift_cut, CEN_CDEF_PX_PRISHIFT0);
+                CEN_IF(sum < 0, CEN_CDEF_PX_NEG);
+                if (pri && sec) {
+                    CEN(CEN_CDEF_PX_BOTH);
+                    CEN_IF(v != iclip(v, (int)mn, mx), CEN_CDEF_PX_CLAMPED);
+                }
+                if (MUT(MUT_CDEF_SENTINEL_SAMPLE)) mn = (unsigned)smn;
+            )
+            if (pri && sec && !MUT(MUT_CDEF_NO_CLAMP)) v = iclip(v, (int)mn, mx);
+            CEN_IF(v == 0, CEN_CDEF_PX_OUT0);
+            CEN_IF(v == bdmax, CEN_CDEF_PX_OUTMAX);
             if (hbd) d16[y * pd + x] = (uint16_t)v;
             else d8[y * pd + x] = (uint8_t)v;
         }
@@ -173,8 +192,16 @@ int oracle_cdef_find_dir(const void *img_, ptrdiff_t stride, unsigned *var, int 
     int best = 0;
     unsigned best_cost = cost[0];
     for (int n = 1; n < 8; n++)
-        if (cost[n] > best_cost) { best_cost = cost[n]; best = n; }
+        if (MUT(MUT_CDEF_TIE_GE) ? cost[n] >= best_cost : cost[n] > best_cost) { best_cost = cost[n]; best = n; }
     *var = (best_cost - cost[best ^ 4]) >> 10;
+    CEN_ONLY(
+        int ties = 0;
+        for (int n = 0; n < 8; n++) ties += cost[n] == best_cost;
+        CEN(CEN_CDEF_TIES + ties);
+        CEN(CEN_CDEF_WIN + best);
+        CEN_IF(ties > 1 && ties < 8, CEN_CDEF_WIN_SUBTIE + best);
+        CEN_IF(!*var, CEN_CDEF_VAR0);
+    )
     return best;
 }
 

@@ -18,12 +18,35 @@
 #include <stdlib.h>
 #include <string.h>
 #include "oracle.h"
+#include "census.h"
 
 #define RUS 390 /* REST_UNIT_STRIDE */
 
 static inline int imin(int a, int b) { return a < b ? a : b; }
 static inline int imax(int a, int b) { return a > b ? a : b; }
 static inline int iclip(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
+
+#ifdef ORACLE_CENSUS
+/* The horizontal Wiener clip with its two events and the mutants that drop one bound. */
+static inline int HCLIP(int v, int lo, int hi)
+{
+    CEN_IF(v < lo, CEN_WIENER_HCLIP_LO);
+    CEN_IF(v > hi, CEN_WIENER_HCLIP_HI);
+    if (v < lo) return MUT(MUT_WIENER_NO_HCLIP_LO) ? v : lo;
+    if (v > hi) return MUT(MUT_WIENER_NO_HCLIP_HI) ? v : hi;
+    return v;
+}
+/* A u32 product shifted down. The mutant reads it as int32: an arithmetic shift, with the
+ * clamp at 0 that a signed table index needs. */
+static inline unsigned SHR_U32(unsigned v, int sh, int mutant)
+{
+    if (MUT(mutant)) return mutant == MUT_SGR_PS_I32 ? (unsigned)imax((int)v >> sh, 0) : (unsigned)((int)v >> sh);
+    return v >> sh;
+}
+#else
+#define HCLIP(v, lo, hi) iclip(v, lo, hi)
+#define SHR_U32(v, sh, mutant) ((v) >> (sh))
+#endif
 
 enum { LR_HAVE_LEFT = 1, LR_HAVE_RIGHT = 2, LR_HAVE_TOP = 4, LR_HAVE_BOTTOM = 8 };
 
@@ -133,7 +156,7 @@ static void wiener(const PX *px, void *p, ptrdiff_t ps, const int (*left)[4], co
         for (int i = 0; i < w; i++) {
             int sum = 1 << (bd + 6);
             for (int k = 0; k < 7; k++) sum += tmp[j * RUS + i + k] * prm->filter[0][k];
-            hor[j * RUS + i] = iclip((sum + (1 << (rbh - 1))) >> rbh, 0, clip_limit - 1);
+            hor[j * RUS + i] = HCLIP((sum + (1 << (rbh - 1))) >> rbh, 0, clip_limit - 1);
         }
     const int rbv = 11 - (bd == 12) * 2;
     const int round_offset = 1 << (bd + (rbv - 1));
@@ -141,6 +164,8 @@ static void wiener(const PX *px, void *p, ptrdiff_t ps, const int (*left)[4], co
         for (int i = 0; i < w; i++) {
             int sum = -round_offset;
             for (int k = 0; k < 7; k++) sum += hor[(j + k) * RUS + i] * prm->filter[1][k];
+            CEN_IF((sum + (1 << (rbv - 1))) >> rbv < 0, CEN_WIENER_VCLIP_LO);
+            CEN_IF((sum + (1 << (rbv - 1))) >> rbv > px->bdmax, CEN_WIENER_VCLIP_HI);
             WR(px, p, j * ps + i, iclip((sum + (1 << (rbv - 1))) >> rbv, 0, px->bdmax));
         }
 }
@@ -180,9 +205,13 @@ static void selfguided(const PX *px, int *dst, const int *src, int w, int h, int
             const int a = (*AA + ((1 << (2 * bdm8)) >> 1)) >> (2 * bdm8);
             const int b = (*BB + ((1 << bdm8) >> 1)) >> bdm8;
             const unsigned p = (unsigned)imax(a * n - b * b, 0);
-            const unsigned z = (p * s + (1u << 19)) >> 20;
+            const unsigned z = SHR_U32(p * s + (1u << 19), 20, MUT_SGR_PS_I32);
             const unsigned x = sgr_x_by_x[z < 255 ? z : 255];
-            *AA = (int)((x * (unsigned)*BB * one_by_x + (1u << 11)) >> 12);
+            CEN_IF(z == 0, CEN_SGR_Z0 + (n == 9));
+            CEN_IF(z >= 255, CEN_SGR_Z255 + (n == 9));
+            CEN_IF(p * s >= 1u << 31, CEN_SGR_PS31 + (n == 9));
+            CEN_IF(x * (unsigned)*BB * one_by_x >= 1u << 31, CEN_SGR_XSUM31 + (n == 9));
+            *AA = (int)SHR_U32(x * (unsigned)*BB * one_by_x + (1u << 11), 12, MUT_SGR_XSUM_I32);
             *BB = (int)x;
         }
     /* A = sumsq (now the scaled b term), B = sum (now x) */
@@ -236,6 +265,8 @@ static void sgr(const PX *px, int kind, void *p, ptrdiff_t ps, const int (*left)
             else if (kind == 1) v = prm->w1 * d1[j * 384 + i];
             else v = prm->w0 * d0[j * 384 + i] + prm->w1 * d1[j * 384 + i];
             const int o = RD(px, p, j * ps + i);
+            CEN_IF(o + ((v + (1 << 10)) >> 11) < 0, CEN_SGR_OUT_LO);
+            CEN_IF(o + ((v + (1 << 10)) >> 11) > px->bdmax, CEN_SGR_OUT_HI);
             WR(px, p, j * ps + i, iclip(o + ((v + (1 << 10)) >> 11), 0, px->bdmax));
         }
 }
@@ -285,8 +316,10 @@ static void lr_stripe(const LrFrame *f, uint8_t *p, ptrdiff_t stride, const int 
         prm.filter[1][2] = prm.filter[1][4] = lr->filter_v[2];
         prm.filter[1][3] = (int16_t)(128 - (prm.filter[1][0] + prm.filter[1][1] + prm.filter[1][2]) * 2);
         kind = -1;
+        CEN(CEN_LR_WIENER + plane);
     } else {
         const int idx = lr->type - RT_SGRPROJ;
+        CEN(CEN_LR_SET + plane * 16 + idx);
         prm.s0 = sgr_params[idx][0];
         prm.s1 = sgr_params[idx][1];
         prm.w0 = lr->sgr_weights[0];

@@ -364,7 +364,11 @@ def make_tilings(w, h, layout, rng):
 
 
 def make_mixed_texture(rng, w, h, bpc):
-    """Blocky content mixing flat and textured 8x8 regions so every deblock branch fires."""
+    """Blocky content mixing flat and textured 8x8 regions. On the small test frames every
+    deblock branch fires somewhere, but thinly: the 16-wide smoother takes tens of lines per
+    frame and its fall-back to the 8-tap one a handful at most, few smoother lines sit near 0
+    or bdmax, and few comparisons land on their limits (profiles/filter_census.md). The frames of
+    tests/directed_filters.py are built for those cases."""
     bdmax = (1 << bpc) - 1
     base = make_texture(rng, w, h, bpc).astype(np.int64)
     amp = np.array([0, 1, 3, 8, 40]) * (bdmax // 255 + 1)

@@ -35,6 +35,55 @@ def load_oracle():
     return o
 
 
+CENSUS_SO = os.path.join(ORACLE_DIR, "liboracle_census.so")
+_census = None
+# oracle_census_layout(i), in this order (oracle/census.h)
+_LAYOUT = ("COUNT", "MUT_COUNT", "LF_NCELL", "LF_CELL_SIZE", "LF_NBR", "LF_NCMP", "LF_NCLIP", "LF_CELL_BRANCH",
+           "LF_CELL_AT", "LF_CELL_AT1", "LF_CELL_PIN_LO", "LF_CELL_PIN_HI", "LF_CELL_CLIP", "LF_CELL_PAIR",
+           "LF", "CDEF_TIES", "CDEF_WIN", "CDEF_WIN_SUBTIE", "CDEF_VAR0", "CDEF_PX_BOTH", "CDEF_PX_CLAMPED",
+           "CDEF_PX_SENTINEL", "CDEF_PX_PRISHIFT0", "CDEF_PX_NEG", "CDEF_PX_OUT0", "CDEF_PX_OUTMAX",
+           "WIENER_HCLIP_LO", "WIENER_HCLIP_HI", "WIENER_VCLIP_LO", "WIENER_VCLIP_HI", "SGR_Z0", "SGR_Z255",
+           "SGR_PS31", "SGR_XSUM31", "SGR_OUT_LO", "SGR_OUT_HI", "LR_SET", "LR_WIENER")
+
+
+class Census:
+    """The census flavour of the three in-loop filter restatements (oracle/census.h): the same
+    sources as liboracle.so with event counters and single-decision mutants. Its state is
+    global, so use it from one thread. Pass `.lib` as `lib=` to deblock_frame, cdef_frame and
+    lr_frame below."""
+
+    def __init__(self, lib):
+        self.lib = lib
+        lib.oracle_census_read.argtypes = [_VP, ctypes.c_int]
+        self.at = {n: lib.oracle_census_layout(i) for i, n in enumerate(_LAYOUT)}
+        assert lib.oracle_census_layout(len(_LAYOUT)) == -1
+
+    def reset(self):
+        self.lib.oracle_census_reset()
+
+    def set_mutant(self, m):
+        self.lib.oracle_census_set_mutant(int(m))
+
+    def read(self):
+        out = np.zeros(self.at["COUNT"], np.uint64)
+        self.lib.oracle_census_read(ptr(out), len(out))
+        return out.astype(np.int64)
+
+    def lf_cells(self, counts):
+        """The deblock counters as [dir][cls][width index 4/6/8/16][LF_CELL_SIZE]."""
+        a = self.at
+        return counts[a["LF"]:a["LF"] + a["LF_NCELL"] * a["LF_CELL_SIZE"]].reshape(2, 2, 4, a["LF_CELL_SIZE"])
+
+
+def load_census():
+    global _census
+    if _census is None:
+        # make compares the time stamps itself
+        subprocess.run(["make", "-s", "-C", ORACLE_DIR, "liboracle_census.so"], check=True)
+        _census = Census(ctypes.CDLL(CENSUS_SO))
+    return _census
+
+
 def ptr(a):
     return ctypes.c_void_p(a.ctypes.data)
 
@@ -58,9 +107,9 @@ def itx_frame(planes, blocks, coef, bpc):
     return arrs[:len(planes)]
 
 
-def deblock_frame(planes, bpc, layout, w, h, lf, sb128=1):
+def deblock_frame(planes, bpc, layout, w, h, lf, sb128=1, lib=None):
     """Oracle whole-frame deblock in the reference's sbrow order; planes modified in place."""
-    o = load_oracle()
+    o = lib or load_oracle()
     f = o.oracle_deblock_frame
     f.restype = None
     f.argtypes = [_VP, _VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _VP,
@@ -78,9 +127,9 @@ def deblock_frame(planes, bpc, layout, w, h, lf, sb128=1):
     return arrs[:len(planes)]
 
 
-def cdef_frame(src_planes, bpc, layout, w, h, masks, cdef):
+def cdef_frame(src_planes, bpc, layout, w, h, masks, cdef, lib=None):
     """Oracle whole-frame CDEF: returns new planes (src untouched). Planes must be 128-aligned."""
-    o = load_oracle()
+    o = lib or load_oracle()
     f = o.oracle_cdef_frame
     f.restype = None
     f.argtypes = [_VP, _VP, _VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _VP,
@@ -99,9 +148,9 @@ def cdef_frame(src_planes, bpc, layout, w, h, masks, cdef):
     return dsts[:len(src_planes)]
 
 
-def lr_frame(cdef_planes, deblocked_planes, bpc, layout, w, h, lr):
+def lr_frame(cdef_planes, deblocked_planes, bpc, layout, w, h, lr, lib=None):
     """Oracle whole-frame loop restoration (in-place reference algorithm on a copy)."""
-    o = load_oracle()
+    o = lib or load_oracle()
     f = o.oracle_lr_frame
     f.restype = None
     f.argtypes = [_VP, _VP, _VP, _VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
