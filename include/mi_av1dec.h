@@ -19,12 +19,13 @@
 #include <stdint.h>
 
 #include "mi_av1dsp.h"
+#include "mi_av1out.h"   /* MiColorInfo */
 
 #ifdef __cplusplus
 extern "C" {
 #endif
 
-#define MI_AV1DEC_ABI_VERSION 3
+#define MI_AV1DEC_ABI_VERSION 4
 
 /* The pass-2 work of one decoded frame. All pointers stay valid until the next
  * mi_dec_next() / mi_dec_destroy() on the same decoder. */
@@ -123,6 +124,9 @@ typedef struct MiDecEvent {
      * of `frame`), and whether that frame was the first decoded of its temporal unit */
     int32_t temporal_id, spatial_id;
     int32_t new_temporal_unit;
+    /* (ABI 4) the colour description of the sequence header of the shown picture's frame
+     * (show_pic >= 0; else of `frame`) */
+    MiColorInfo color;
 } MiDecEvent;
 
 /* ---- device execution of a decoded frame (these two live in librav1d_amd.so) ----
@@ -246,6 +250,17 @@ int  mi_dec_send(MiDec *d, const uint8_t *data, size_t size);
 /* Next event: 1 and *ev filled, 0 when none is pending, or -errno. */
 int  mi_dec_next(MiDec *d, MiDecEvent *ev);
 const char *mi_dec_error(const MiDec *d);
+
+/* What a sequence header says about the pictures to come (Dav1dSequenceHeader's profile,
+ * max_width / max_height, hbd, layout, film_grain_present and colour description). */
+typedef struct MiSeqInfo {
+    int32_t profile, max_w, max_h, bpc, layout, film_grain_present;
+    MiColorInfo color;
+} MiSeqInfo;
+/* dav1d_parse_sequence_header (src/lib.rs): scan the OBUs of `data` and fill *out from the first
+ * sequence header, without decoding anything. 0; -ENOENT when there is none; -EINVAL for null
+ * arguments, a malformed OBU or a malformed sequence header. No decoder is needed. */
+int  mi_dec_parse_sequence_header(const uint8_t *data, size_t size, MiSeqInfo *out);
 
 #ifdef __cplusplus
 }

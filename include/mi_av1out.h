@@ -3,7 +3,8 @@
  * host (film grain fused with the copy) and the reference's output muxers.
  *
  * Two libraries implement it:
- *   - librav1d_amd.so (gfx950): mi_host_picture_alloc / _free, mi_output_picture;
+ *   - librav1d_amd.so (gfx950): mi_host_picture_alloc / _free, mi_output_picture, and the
+ *     display output that stays on the device, mi_display_picture;
  *   - libmi_av1dec.so (host C++): the muxers mi_muxer_* (no GPU code).
  *
  * Reference: the CLI's output stage (tools/output/output.rs), its muxers md5
@@ -51,6 +52,12 @@ typedef struct MiOutParams {
     int32_t render_w, render_h;
 } MiOutParams;
 
+/* The sequence header's colour description (Dav1dSequenceHeader: include/dav1d/headers.rs), with
+ * the values of Dav1dColorPrimaries, Dav1dTransferCharacteristics, Dav1dMatrixCoefficients,
+ * color_range (0 limited, 1 full) and Dav1dChromaSamplePosition (0 unknown, 1 vertical,
+ * 2 colocated). 2 is "unspecified" for pri, trc and mtrx. */
+typedef struct MiColorInfo { int32_t pri, trc, mtrx, range, chr; } MiColorInfo;
+
 typedef struct MiMuxer MiMuxer;
 
 /* name: "md5", "yuv", "y4m2" or "null" (tools/output/output.rs muxer table). file: a path, or
@@ -69,6 +76,51 @@ int  mi_muxer_verify(MiMuxer *m, const char *md5_str);
 int  mi_muxer_digest(MiMuxer *m, char out[33]);
 /* Write the trailer (md5: the digest line), close the file, free the muxer. */
 void mi_muxer_close(MiMuxer *m);
+
+/* ---- device display output (librav1d_amd.so) --------------------------------------------- */
+
+/* A shown picture for a consumer on the device: tight (no 128-alignment; the strides are the
+ * caller's, only w x h is written), with film grain, as semi-planar YUV or as R'G'B'.
+ *
+ * MI_OUT_SEMIPLANAR: data[0] = Y, data[1] = interleaved UV at the source's own subsampling
+ *   (NV12 / P010 for 4:2:0, NV16 / P210 for 4:2:2, NV24 for 4:4:4; 4:0:0 writes Y only).
+ *   8 bpc: u8; 10 / 12 bpc: u16, MSB-aligned (v << (16 - bpc), the P010 / P012 convention).
+ * MI_OUT_RGB_PLANAR: data[0..2] = the R, G, B planes, w x h each; u8 at 8 bpc, else u16
+ *   LSB-aligned; full range at the source bit depth.
+ * MI_OUT_RGBA_PACKED: data[0] = h x w x 4 samples of the same type, A = 2^bpc - 1.
+ *
+ * The RGB formats upsample the chroma with integer arithmetic and clamped indices, the vertical
+ * pass first (cw x ch = the chroma plane size):
+ *   vertical, 4:2:0, chr == 2 (co-located): row 2j = c[j], row 2j+1 = (c[j] + c[min(j+1, ch-1)] + 1) >> 1;
+ *   vertical, 4:2:0, chr 0 or 1 (centred):  row 2j = (c[max(j-1, 0)] + 3 c[j] + 2) >> 2,
+ *                                            row 2j+1 = (3 c[j] + c[min(j+1, ch-1)] + 2) >> 2;
+ *   horizontal, 4:2:0 and 4:2:2: column 2i = c[i], column 2i+1 = (c[i] + c[min(i+1, cw-1)] + 1) >> 1.
+ * and convert with 14-bit fixed-point coefficients computed on the host from color->mtrx
+ * (1, 4, 5, 6, 7, 9), color->range and the bit depth (b = bpc, M = 2^b - 1, H = 2^(b-1), S = 14;
+ * limited: Yo = 16 << (b-8), ky = round(2^S M / (219 << (b-8))), kc = M / (224 << (b-8)); full:
+ * Yo = 0, ky = 2^S, kc = 1; crv = round(2^S 2(1-Kr) kc), cbu = round(2^S 2(1-Kb) kc),
+ * cgu = round(2^S 2 Kb(1-Kb)/Kg kc), cgv = round(2^S 2 Kr(1-Kr)/Kg kc), Kg = 1 - Kr - Kb):
+ *   R = clip((ky (y-Yo) + crv (v-H) + 2^(S-1)) >> S, 0, M)
+ *   G = clip((ky (y-Yo) - cgu (u-H) - cgv (v-H) + 2^(S-1)) >> S, 0, M)
+ *   B = clip((ky (y-Yo) + cbu (u-H) + 2^(S-1)) >> S, 0, M)
+ * mtrx 0 (identity, 4:4:4 only): G = Y, B = U, R = V. 4:0:0: R = G = B from the luma term. No
+ * transfer-function or primaries conversion: the output is R'G'B' in the stream's primaries. */
+enum { MI_OUT_SEMIPLANAR = 0, MI_OUT_RGB_PLANAR = 1, MI_OUT_RGBA_PACKED = 2 };
+typedef struct MiDisplayImage {
+    void *data[3]; ptrdiff_t stride[3];   /* bytes; any device-accessible memory */
+    int32_t w, h, format, bpc;            /* w x h = the visible size of `in` */
+} MiDisplayImage;
+
+/* Enqueue the display output of `in` on `stream` (never synchronises). With `fg`, film grain is
+ * applied first (mi_film_grain_frame, mtrx_identity = color && color->mtrx == 0) into a scratch
+ * picture the context owns (allocated on first use, kept while the geometry stays the same) and
+ * the conversion reads that. `color` may be NULL for MI_OUT_SEMIPLANAR.
+ * Every check precedes any device work: -EINVAL for a null or malformed argument, a size or bpc
+ * that differs from `in`, an unknown format, an RGB format with NULL `color` or mtrx 2
+ * (unspecified: the caller has to choose), identity without 4:4:4; -ENOTSUP for matrices 8 and
+ * 10-14; -ENOMEM, -EIO. */
+int mi_display_picture(MiCtx *ctx, const MiPicture *in, const MiDisplayImage *out,
+                       const MiColorInfo *color, const MiFilmGrainData *fg, void *stream);
 
 #ifdef __cplusplus
 }

@@ -46,6 +46,23 @@ class MiDecFrame(ctypes.Structure):
                 ("q_nstrips", ctypes.c_int32), ("q_granules", ctypes.c_int32)]
 
 
+class MiColorInfo(ctypes.Structure):
+    """include/mi_av1out.h: the sequence header's colour description (Dav1dColorPrimaries,
+    Dav1dTransferCharacteristics, Dav1dMatrixCoefficients, color_range, Dav1dChromaSamplePosition)."""
+    _fields_ = [("pri", ctypes.c_int32), ("trc", ctypes.c_int32), ("mtrx", ctypes.c_int32),
+                ("range", ctypes.c_int32), ("chr", ctypes.c_int32)]
+
+    def astuple(self):
+        return (self.pri, self.trc, self.mtrx, self.range, self.chr)
+
+
+class MiSeqInfo(ctypes.Structure):
+    """include/mi_av1dec.h: what mi_dec_parse_sequence_header reads from a sequence header."""
+    _fields_ = [("profile", ctypes.c_int32), ("max_w", ctypes.c_int32), ("max_h", ctypes.c_int32),
+                ("bpc", ctypes.c_int32), ("layout", ctypes.c_int32), ("film_grain_present", ctypes.c_int32),
+                ("color", MiColorInfo)]
+
+
 class MiDecEvent(ctypes.Structure):
     _fields_ = [("frame", ctypes.POINTER(MiDecFrame)), ("pic_id", ctypes.c_int32),
                 ("ref_pic", ctypes.c_int32 * 7), ("show_pic", ctypes.c_int32),
@@ -53,7 +70,7 @@ class MiDecEvent(ctypes.Structure):
                 ("release", ctypes.POINTER(ctypes.c_int32)), ("n_release", ctypes.c_int32),
                 ("mtrx_identity", ctypes.c_int32),
                 ("temporal_id", ctypes.c_int32), ("spatial_id", ctypes.c_int32),
-                ("new_temporal_unit", ctypes.c_int32)]
+                ("new_temporal_unit", ctypes.c_int32), ("color", MiColorInfo)]
 
 
 def build_dec():
@@ -80,6 +97,7 @@ def dec_lib():
         d.mi_dec_drain.argtypes = [ctypes.c_void_p]
         d.mi_dec_error.argtypes = [ctypes.c_void_p]
         d.mi_dec_error.restype = ctypes.c_char_p
+        d.mi_dec_parse_sequence_header.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(MiSeqInfo)]
         _dec = d
     return _dec
 
@@ -245,6 +263,18 @@ class Av1Decoder:
 
     def error(self):
         return self.lib.mi_dec_error(self.h).decode()
+
+    @staticmethod
+    def parse_sequence_header(data):
+        """mi_dec_parse_sequence_header (dav1d_parse_sequence_header, src/lib.rs): the MiSeqInfo of
+        the first sequence header among the OBUs of `data`, without decoding. Raises DecoderError
+        with code -ENOENT when there is none, -EINVAL when it is malformed."""
+        out = MiSeqInfo()
+        data = bytes(data)
+        r = dec_lib().mi_dec_parse_sequence_header(data, len(data), ctypes.byref(out))
+        if r < 0:
+            raise DecoderError("mi_dec_parse_sequence_header", r, os.strerror(-r))
+        return out
 
     def send(self, data):
         r = self.lib.mi_dec_send(self.h, data, len(data))

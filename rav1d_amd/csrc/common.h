@@ -487,6 +487,26 @@ int init_fg_tables();
 int launch_fg(const FgArgs &a, hipStream_t s, bool prep, bool apply);
 int launch_fg_call(const FgArgs &a, hipStream_t s);
 
+// display output (display.hip): the visible w x h of a picture as semi-planar YUV or R'G'B'.
+// One lane converts 8 luma columns of one luma row (4:0:0, 4:2:2, 4:4:4) or of the row pair that
+// shares a chroma row (4:2:0).
+struct DisplayArgs {
+    const uint8_t *src[3];
+    int64_t sstride[2];
+    uint8_t *dst[3];
+    int64_t dstride[3];
+    int w, h, cw, ch;             // luma and chroma plane sizes
+    int ss_hor, ss_ver, mono;
+    int coloc;                    // 4:2:0 vertical siting: chr == 2 (else centred)
+    int identity;                 // mtrx 0: G = Y, B = U, R = V
+    int shift;                    // semi-planar: 16 - bpc for 10 / 12 bpc, else 0
+    int yo, half, maxv;           // Yo, H, M
+    int ky, crv, cbu, cgu, cgv;   // 14-bit fixed point
+    int svec, dvec;               // bit p: plane p's pointer and stride are 16-byte aligned
+    int chunks, units;            // 8-column runs per row, row units (rows, or row pairs)
+};
+int launch_display(const DisplayArgs &a, int bpc, int format, hipStream_t s);
+
 // ---- per-call (table-compatible) entry points: single-block kernels ----
 struct LfCallArgs {
     uint8_t *dst;

@@ -13,6 +13,10 @@ struct MiCtx {
     uint8_t *fg_scaling = nullptr;
     uint8_t *fg_offsets = nullptr;
     size_t fg_offsets_bytes = 0;
+    // mi_display_picture with grain: the grained picture the converter reads (one allocation in
+    // the geometry of the shown picture, replaced only when a picture needs more)
+    uint8_t *disp_fg = nullptr;
+    size_t disp_fg_bytes = 0;
     // persistent intra reconstruction: per-block done epochs, queue heads, error word
     uint32_t *ir_done = nullptr;
     size_t ir_done_n = 0;
@@ -69,6 +73,7 @@ struct MiCtx {
         if (fg_lut) (void)hipFree(fg_lut);
         if (fg_scaling) (void)hipFree(fg_scaling);
         if (fg_offsets) (void)hipFree(fg_offsets);
+        if (disp_fg) (void)hipFree(disp_fg);
     }
 };
 

@@ -1,0 +1,416 @@
+// display.hip — mi_display_picture (include/mi_av1out.h): a shown picture for a consumer on the
+// device. The decoder's pictures are planar in the 128-aligned allocator geometry and carry no
+// film grain; this pass writes the visible w x h tight into the caller's memory as semi-planar
+// YUV (NV12 / P010 and their 4:2:2 / 4:4:4 kin) or as R'G'B' (planar, or packed with alpha),
+// after mi_film_grain_frame when the frame has grain.
+//
+// display_kernel is a pure streaming pass (4:2:0: 1.5 W H B read, 3 or 4 W H B written). One lane
+// owns 8 luma columns of one row unit: one luma row, or for 4:2:0 the row pair 2j, 2j+1 that
+// shares chroma row j, so the chroma rows j-1, j, j+1 the pair interpolates from are loaded once
+// into registers (4 samples and one halo sample each) and serve both rows. Loads and stores are
+// one vector per run (8 B for 8 u8 samples, 16 B otherwise) where the plane's pointer and stride
+// are 16-byte aligned and the run lies inside the row; any other run is done sample by sample
+// with clamped source columns. Packed RGBA, whose runs are 2 or 4 vectors long, goes through a
+// per-wave LDS hand-off so that a store instruction writes 1 KB contiguously (rgb_row).
+#include <cerrno>
+#include <cmath>
+#include <cstring>
+
+#include "mi_av1out.h"
+#include "ctx.h"
+
+namespace mi {
+namespace {
+
+constexpr int kDispS = 14;   // fixed-point fraction bits of the matrix
+
+// N samples of a plane row from column x0, columns clamped to pw - 1
+template <typename Px, int N>
+__device__ __forceinline__ void load_run(const uint8_t *row, int x0, int pw, bool vec, int (&v)[N]) {
+    const Px *p = reinterpret_cast<const Px *>(row);
+    constexpr int kBytes = N * (int)sizeof(Px);
+    static_assert(kBytes == 4 || kBytes == 8 || kBytes == 16, "one vector per run");
+    if (vec && x0 + N <= pw) {
+        uint32_t q[kBytes / 4];
+        if constexpr (kBytes == 16) {
+            const uint4 t = *reinterpret_cast<const uint4 *>(p + x0);
+            q[0] = t.x; q[1] = t.y; q[2] = t.z; q[3] = t.w;
+        } else if constexpr (kBytes == 8) {
+            const uint2 t = *reinterpret_cast<const uint2 *>(p + x0);
+            q[0] = t.x; q[1] = t.y;
+        } else {
+            q[0] = *reinterpret_cast<const uint32_t *>(p + x0);
+        }
+#pragma unroll
+        for (int k = 0; k < N; k++)
+            v[k] = sizeof(Px) == 1 ? (int)((q[k >> 2] >> (8 * (k & 3))) & 0xff) : (int)((q[k >> 1] >> (16 * (k & 1))) & 0xffff);
+    } else {
+#pragma unroll
+        for (int k = 0; k < N; k++) v[k] = (int)p[min(x0 + k, pw - 1)];
+    }
+}
+
+// N samples to a destination row at sample s0; the row holds `limit` samples
+template <typename Px, int N>
+__device__ __forceinline__ void store_run(uint8_t *row, int s0, int limit, bool vec, const int (&v)[N]) {
+    Px *p = reinterpret_cast<Px *>(row);
+    constexpr int kBytes = N * (int)sizeof(Px);
+    static_assert(kBytes == 8 || kBytes % 16 == 0, "whole vectors per run");
+    if (vec && s0 + N <= limit) {
+        uint32_t q[kBytes / 4];
+#pragma unroll
+        for (int i = 0; i < kBytes / 4; i++) {
+            if constexpr (sizeof(Px) == 1)
+                q[i] = (uint32_t)v[4 * i] | ((uint32_t)v[4 * i + 1] << 8) | ((uint32_t)v[4 * i + 2] << 16) |
+                       ((uint32_t)v[4 * i + 3] << 24);
+            else
+                q[i] = (uint32_t)v[2 * i] | ((uint32_t)v[2 * i + 1] << 16);
+        }
+        if constexpr (kBytes == 8) {
+            *reinterpret_cast<uint2 *>(p + s0) = make_uint2(q[0], q[1]);
+        } else {
+#pragma unroll
+            for (int i = 0; i < kBytes / 16; i++)
+                reinterpret_cast<uint4 *>(p + s0)[i] = make_uint4(q[4 * i], q[4 * i + 1], q[4 * i + 2], q[4 * i + 3]);
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < N; k++)
+            if (s0 + k < limit) p[s0 + k] = (Px)v[k];
+    }
+}
+
+// chroma columns cx0 .. cx0 + 3 of one row and, in `halo`, column cx0 + 4 (the right neighbour
+// of the last odd luma column)
+template <typename Px>
+__device__ __forceinline__ void load5(const uint8_t *row, int cx0, int cw, bool vec, int (&v)[4], int &halo) {
+    load_run<Px, 4>(row, cx0, cw, vec, v);
+    halo = (int)reinterpret_cast<const Px *>(row)[min(cx0 + 4, cw - 1)];
+}
+
+// the vertical pass of 4:2:0 for one column: c = row j, cp = row max(j-1, 0), cn = row min(j+1, ch-1)
+__device__ __forceinline__ void vert420(bool coloc, int cp, int c, int cn, int &even, int &odd) {
+    even = coloc ? c : (cp + 3 * c + 2) >> 2;
+    odd = coloc ? (c + cn + 1) >> 1 : (3 * c + cn + 2) >> 2;
+}
+
+// the horizontal pass over 4 columns and their halo
+__device__ __forceinline__ void horz(const int (&v)[4], int halo, int (&o)[8]) {
+    o[0] = v[0]; o[1] = (v[0] + v[1] + 1) >> 1;
+    o[2] = v[1]; o[3] = (v[1] + v[2] + 1) >> 1;
+    o[4] = v[2]; o[5] = (v[2] + v[3] + 1) >> 1;
+    o[6] = v[3]; o[7] = (v[3] + halo + 1) >> 1;
+}
+
+// chroma plane p at luma resolution for the lane's 8 columns of row unit u: up[r] = luma row
+// u * (1 + ss_ver) + r. The vertical pass gives integer rows, the horizontal pass runs over them.
+template <typename Px>
+__device__ __forceinline__ void upsample(const DisplayArgs &a, int p, int u, int x0, int (&up)[2][8]) {
+    const uint8_t *base = a.src[p];
+    const int64_t st = a.sstride[1];
+    const bool vec = (a.svec >> p) & 1;
+    int t0[8], t1[8];   // (both rows are always set, and stored to `up` in one place, so that
+                        // they stay in registers; t1 is used by 4:2:0 only)
+    if (!a.ss_hor) {   // 4:4:4
+        load_run<Px, 8>(base + u * st, x0, a.cw, vec, t0);
+#pragma unroll
+        for (int k = 0; k < 8; k++) t1[k] = t0[k];
+    } else {
+        const int cx0 = x0 >> 1;
+        int c[4], hc, e[4], he, o[4], ho;
+        load5<Px>(base + u * st, cx0, a.cw, vec, c, hc);
+        if (!a.ss_ver) {   // 4:2:2
+#pragma unroll
+            for (int k = 0; k < 4; k++) e[k] = o[k] = c[k];
+            he = ho = hc;
+        } else {
+            int cn[4], hn, cp[4], hp;
+            load5<Px>(base + min(u + 1, a.ch - 1) * st, cx0, a.cw, vec, cn, hn);
+            // (co-located: the row above is not needed; re-reading row u keeps one code path)
+            load5<Px>(base + (a.coloc ? u : max(u - 1, 0)) * st, cx0, a.cw, vec, cp, hp);
+#pragma unroll
+            for (int k = 0; k < 4; k++) vert420(a.coloc, cp[k], c[k], cn[k], e[k], o[k]);
+            vert420(a.coloc, hp, hc, hn, he, ho);
+        }
+        horz(e, he, t0);
+        horz(o, ho, t1);
+    }
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        up[0][k] = t0[k];
+        up[1][k] = t1[k];
+    }
+}
+
+// 8 pixels of luma row `row` to R'G'B'
+template <typename Px, int FMT>
+__device__ __forceinline__ void rgb_row(const DisplayArgs &a, int row, int x0, const int (&y)[8], const int (&cu)[8],
+                                        const int (&cv)[8]) {
+    constexpr int kRound = 1 << (kDispS - 1);
+    int R[8], G[8], B[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        if (a.identity) {
+            G[k] = y[k];
+            B[k] = cu[k];
+            R[k] = cv[k];
+        } else {
+            const int l = a.ky * (y[k] - a.yo) + kRound;
+            int rr = l, gg = l, bb = l;
+            if (!a.mono) {
+                const int cb = cu[k] - a.half, cr = cv[k] - a.half;
+                rr += a.crv * cr;
+                gg -= a.cgu * cb + a.cgv * cr;
+                bb += a.cbu * cb;
+            }
+            R[k] = min(max(rr >> kDispS, 0), a.maxv);
+            G[k] = min(max(gg >> kDispS, 0), a.maxv);
+            B[k] = min(max(bb >> kDispS, 0), a.maxv);
+        }
+    }
+    if constexpr (FMT == MI_OUT_RGB_PLANAR) {
+        store_run<Px, 8>(a.dst[0] + row * a.dstride[0], x0, a.w, a.dvec & 1, R);
+        store_run<Px, 8>(a.dst[1] + row * a.dstride[1], x0, a.w, (a.dvec >> 1) & 1, G);
+        store_run<Px, 8>(a.dst[2] + row * a.dstride[2], x0, a.w, (a.dvec >> 2) & 1, B);
+    } else {
+        int o[32];
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            o[4 * k] = R[k];
+            o[4 * k + 1] = G[k];
+            o[4 * k + 2] = B[k];
+            o[4 * k + 3] = a.maxv;
+        }
+        uint8_t *drow = a.dst[0] + row * a.dstride[0];
+        // A lane's run is 32 samples (2 or 4 16-B vectors), so lane-owned stores would put each
+        // store instruction's 64 vectors 32 or 64 B apart. Where the wave's 64 runs all lie inside
+        // the row of an aligned plane (wave-uniform: a wave is one row unit's 512 columns), the
+        // wave hands its runs through LDS and consecutive lanes store consecutive vectors.
+        constexpr int kVec = 32 * (int)sizeof(Px) / 16;
+        const int xw = x0 - 8 * (int)threadIdx.x;   // the wave's first column
+        if ((a.dvec & 1) && xw + 512 <= a.w) {
+            __shared__ uint4 tile[4][64 * kVec];
+            uint4 *t = tile[threadIdx.y];
+#pragma unroll
+            for (int i = 0; i < kVec; i++) {
+                uint32_t q[4];
+#pragma unroll
+                for (int j = 0; j < 4; j++) {
+                    const int k = 4 * i + j;   // 32-bit word k of the run
+                    if constexpr (sizeof(Px) == 1)
+                        q[j] = (uint32_t)o[4 * k] | ((uint32_t)o[4 * k + 1] << 8) | ((uint32_t)o[4 * k + 2] << 16) |
+                               ((uint32_t)o[4 * k + 3] << 24);
+                    else
+                        q[j] = (uint32_t)o[2 * k] | ((uint32_t)o[2 * k + 1] << 16);
+                }
+                t[threadIdx.x * kVec + i] = make_uint4(q[0], q[1], q[2], q[3]);
+            }
+            // the wave's own LDS traffic is ordered; keep the compiler from moving it
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            uint4 *d = reinterpret_cast<uint4 *>(drow + (int64_t)xw * 4 * (int)sizeof(Px));
+#pragma unroll
+            for (int i = 0; i < kVec; i++) d[i * 64 + threadIdx.x] = t[i * 64 + threadIdx.x];
+            // (the next row's hand-off rewrites the tile)
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+        } else {
+            store_run<Px, 32>(drow, 4 * x0, 4 * a.w, a.dvec & 1, o);
+        }
+    }
+}
+
+template <typename Px, int FMT>
+__global__ __launch_bounds__(256) void display_kernel(const DisplayArgs a) {
+    const int cx = blockIdx.x * 64 + threadIdx.x, u = blockIdx.y * 4 + threadIdx.y;
+    if (cx >= a.chunks || u >= a.units) return;
+    const int x0 = cx * 8, nrows = 1 + a.ss_ver, r0 = u * nrows;
+    int y[2][8];
+    load_run<Px, 8>(a.src[0] + r0 * a.sstride[0], x0, a.w, a.svec & 1, y[0]);
+    if (a.ss_ver) {
+        load_run<Px, 8>(a.src[0] + min(r0 + 1, a.h - 1) * a.sstride[0], x0, a.w, a.svec & 1, y[1]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 8; k++) y[1][k] = y[0][k];   // (not used)
+    }
+
+    if constexpr (FMT == MI_OUT_SEMIPLANAR) {
+#pragma unroll
+        for (int r = 0; r < 2; r++) {
+            if (r < nrows && r0 + r < a.h) {
+                int o[8];
+#pragma unroll
+                for (int k = 0; k < 8; k++) o[k] = y[r][k] << a.shift;
+                store_run<Px, 8>(a.dst[0] + (int64_t)(r0 + r) * a.dstride[0], x0, a.w, a.dvec & 1, o);
+            }
+        }
+        if (a.mono) return;
+        // chroma row u (the row unit is a chroma row for 4:2:0, a luma row otherwise)
+        uint8_t *drow = a.dst[1] + u * a.dstride[1];
+        const uint8_t *urow = a.src[1] + u * a.sstride[1], *vrow = a.src[2] + u * a.sstride[1];
+        if (a.ss_hor) {
+            int cu[4], cv[4], o[8];
+            load_run<Px, 4>(urow, x0 >> 1, a.cw, (a.svec >> 1) & 1, cu);
+            load_run<Px, 4>(vrow, x0 >> 1, a.cw, (a.svec >> 2) & 1, cv);
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                o[2 * k] = cu[k] << a.shift;
+                o[2 * k + 1] = cv[k] << a.shift;
+            }
+            store_run<Px, 8>(drow, x0, 2 * a.cw, (a.dvec >> 1) & 1, o);
+        } else {
+            int cu[8], cv[8], o[16];
+            load_run<Px, 8>(urow, x0, a.cw, (a.svec >> 1) & 1, cu);
+            load_run<Px, 8>(vrow, x0, a.cw, (a.svec >> 2) & 1, cv);
+#pragma unroll
+            for (int k = 0; k < 8; k++) {
+                o[2 * k] = cu[k] << a.shift;
+                o[2 * k + 1] = cv[k] << a.shift;
+            }
+            store_run<Px, 16>(drow, 2 * x0, 2 * a.cw, (a.dvec >> 1) & 1, o);
+        }
+    } else {
+        int cu[2][8] = {}, cv[2][8] = {};
+        if (!a.mono) {
+            upsample<Px>(a, 1, u, x0, cu);
+            upsample<Px>(a, 2, u, x0, cv);
+        }
+        rgb_row<Px, FMT>(a, r0, x0, y[0], cu[0], cv[0]);
+        if (a.ss_ver && r0 + 1 < a.h) rgb_row<Px, FMT>(a, r0 + 1, x0, y[1], cu[1], cv[1]);
+    }
+}
+
+template <typename Px>
+int launch_px(const DisplayArgs &a, int format, hipStream_t s) {
+    const dim3 block(64, 4), grid((a.chunks + 63) / 64, (a.units + 3) / 4);
+    switch (format) {
+    case MI_OUT_SEMIPLANAR: display_kernel<Px, MI_OUT_SEMIPLANAR><<<grid, block, 0, s>>>(a); break;
+    case MI_OUT_RGB_PLANAR: display_kernel<Px, MI_OUT_RGB_PLANAR><<<grid, block, 0, s>>>(a); break;
+    default: display_kernel<Px, MI_OUT_RGBA_PACKED><<<grid, block, 0, s>>>(a); break;
+    }
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+}  // namespace
+
+int launch_display(const DisplayArgs &a, int bpc, int format, hipStream_t s) {
+    return bpc == 8 ? launch_px<uint8_t>(a, format, s) : launch_px<uint16_t>(a, format, s);
+}
+
+}  // namespace mi
+
+namespace {
+
+// (Kr, Kb) of Dav1dMatrixCoefficients: 0 supported, -ENOTSUP (a matrix that is no Kr / Kb
+// matrix: YCgCo, BT.2020 constant luminance, SMPTE 2085, chromaticity-derived, ICtCp) or -EINVAL
+int matrix_k(int mtrx, double *kr, double *kb) {
+    switch (mtrx) {
+    case 1: *kr = 0.2126; *kb = 0.0722; return 0;    // BT.709
+    case 4: *kr = 0.30; *kb = 0.11; return 0;        // FCC
+    case 5:                                          // BT.470BG
+    case 6: *kr = 0.299; *kb = 0.114; return 0;      // BT.601
+    case 7: *kr = 0.212; *kb = 0.087; return 0;      // SMPTE 240
+    case 9: *kr = 0.2627; *kb = 0.0593; return 0;    // BT.2020 non-constant luminance
+    case 8: case 10: case 11: case 12: case 13: case 14: return -ENOTSUP;
+    default: return -EINVAL;
+    }
+}
+
+int round_fix(double v) { return (int)floor(v * (double)(1 << mi::kDispS) + 0.5); }
+
+bool aligned16(const void *p, ptrdiff_t stride) { return (((uintptr_t)p | (uintptr_t)stride) & 15) == 0; }
+
+}  // namespace
+
+extern "C" int mi_display_picture(MiCtx *ctx, const MiPicture *in, const MiDisplayImage *out, const MiColorInfo *color,
+                                  const MiFilmGrainData *fg, void *stream) {
+    if (!in || !out || !in->data[0] || in->w <= 0 || in->h <= 0 || in->w > 65536 || in->h > 65536 ||
+        in->layout < 0 || in->layout > 3 || (in->bpc != 8 && in->bpc != 10 && in->bpc != 12) || in->stride[0] <= 0)
+        return -EINVAL;
+    if (in->layout && (!in->data[1] || !in->data[2] || in->stride[1] <= 0)) return -EINVAL;
+    if (out->w != in->w || out->h != in->h || out->bpc != in->bpc) return -EINVAL;
+    if (out->format != MI_OUT_SEMIPLANAR && out->format != MI_OUT_RGB_PLANAR && out->format != MI_OUT_RGBA_PACKED)
+        return -EINVAL;
+    const int pxb = in->bpc == 8 ? 1 : 2, ss_hor = in->layout == 1 || in->layout == 2, ss_ver = in->layout == 1;
+    const int cw = (in->w + ss_hor) >> ss_hor, ch = (in->h + ss_ver) >> ss_ver;
+    // destination planes and the samples a row of each holds
+    const int ndst = out->format == MI_OUT_RGB_PLANAR ? 3 : out->format == MI_OUT_SEMIPLANAR && in->layout ? 2 : 1;
+    for (int p = 0; p < ndst; p++) {
+        const int64_t samples = out->format == MI_OUT_RGBA_PACKED ? 4 * (int64_t)in->w
+                              : out->format == MI_OUT_SEMIPLANAR && p ? 2 * (int64_t)cw : in->w;
+        if (!out->data[p] || out->stride[p] < samples * pxb) return -EINVAL;
+        if (((uintptr_t)out->data[p] | (uintptr_t)out->stride[p]) & (uintptr_t)(pxb - 1)) return -EINVAL;
+    }
+    if ((int64_t)in->stride[0] < (int64_t)in->w * pxb || (in->layout && (int64_t)in->stride[1] < (int64_t)cw * pxb))
+        return -EINVAL;
+
+    mi::DisplayArgs a;
+    memset(&a, 0, sizeof(a));
+    if (out->format != MI_OUT_SEMIPLANAR) {
+        if (!color || color->mtrx == 2 || (color->range != 0 && color->range != 1)) return -EINVAL;
+        if (color->mtrx == 0) {
+            if (in->layout != 3) return -EINVAL;
+            a.identity = 1;
+        } else {
+            double kr, kb;
+            if (int e = matrix_k(color->mtrx, &kr, &kb)) return e;
+            const int b = in->bpc;
+            const double m = (double)((1 << b) - 1), kg = 1.0 - kr - kb;
+            const double kc = color->range ? 1.0 : m / (double)(224 << (b - 8));
+            a.yo = color->range ? 0 : 16 << (b - 8);
+            a.ky = color->range ? 1 << mi::kDispS : round_fix(m / (double)(219 << (b - 8)));
+            a.crv = round_fix(2.0 * (1.0 - kr) * kc);
+            a.cbu = round_fix(2.0 * (1.0 - kb) * kc);
+            a.cgu = round_fix(2.0 * kb * (1.0 - kb) / kg * kc);
+            a.cgv = round_fix(2.0 * kr * (1.0 - kr) / kg * kc);
+        }
+    }
+    if (!ctx) return -EINVAL;
+
+    MiPicture src = *in;
+    if (fg) {
+        // the grained picture, in the geometry of `in`
+        const size_t ah = ((size_t)in->h + 127) & ~(size_t)127;
+        const size_t ybytes = ((size_t)in->stride[0] * ah + 255) & ~(size_t)255;
+        const size_t cbytes = in->layout ? ((size_t)in->stride[1] * (ah >> ss_ver) + 255) & ~(size_t)255 : 0;
+        if (ybytes + 2 * cbytes > ctx->disp_fg_bytes) {
+            if (ctx->disp_fg) (void)hipFree(ctx->disp_fg);   // (waits for the work that reads it)
+            ctx->disp_fg = nullptr;
+            ctx->disp_fg_bytes = 0;
+            if (hipMalloc(&ctx->disp_fg, ybytes + 2 * cbytes) != hipSuccess) return ctx->last_error = -ENOMEM;
+            ctx->disp_fg_bytes = ybytes + 2 * cbytes;
+        }
+        src.data[0] = ctx->disp_fg;
+        src.data[1] = in->layout ? ctx->disp_fg + ybytes : nullptr;
+        src.data[2] = in->layout ? ctx->disp_fg + ybytes + cbytes : nullptr;
+        if (int e = mi_film_grain_frame(ctx, in, &src, fg, color && color->mtrx == 0, stream)) return e;
+    }
+
+    for (int p = 0; p < (in->layout ? 3 : 1); p++) {
+        a.src[p] = (const uint8_t *)src.data[p];
+        if (aligned16(src.data[p], src.stride[p ? 1 : 0])) a.svec |= 1 << p;
+    }
+    a.sstride[0] = src.stride[0];
+    a.sstride[1] = src.stride[1];
+    for (int p = 0; p < ndst; p++) {
+        a.dst[p] = (uint8_t *)out->data[p];
+        a.dstride[p] = out->stride[p];
+        if (aligned16(out->data[p], out->stride[p])) a.dvec |= 1 << p;
+    }
+    a.w = in->w;
+    a.h = in->h;
+    a.cw = cw;
+    a.ch = ch;
+    a.ss_hor = ss_hor;
+    a.ss_ver = ss_ver;
+    a.mono = in->layout == 0;
+    a.coloc = color && color->chr == 2;
+    a.shift = out->format == MI_OUT_SEMIPLANAR && in->bpc > 8 ? 16 - in->bpc : 0;
+    a.half = 1 << (in->bpc - 1);
+    a.maxv = (1 << in->bpc) - 1;
+    a.chunks = (in->w + 7) >> 3;
+    a.units = ss_ver ? ch : in->h;
+    if (mi::launch_display(a, in->bpc, out->format, (hipStream_t)stream)) return ctx->last_error = -EIO;
+    return 0;
+}

@@ -116,6 +116,7 @@ int mi_dec_next(MiDec *d, MiDecEvent *ev) {
     ev->temporal_id = e.temporal_id;
     ev->spatial_id = e.spatial_id;
     ev->new_temporal_unit = e.new_tu;
+    ev->color = e.color;
     d->release.assign(e.release.begin(), e.release.end());
     ev->release = d->release.data();
     ev->n_release = (int32_t)d->release.size();
@@ -129,6 +130,21 @@ int mi_dec_next(MiDec *d, MiDecEvent *ev) {
         ev->frame = &f;
     }
     return 1;
+}
+
+int mi_dec_parse_sequence_header(const uint8_t *data, size_t size, MiSeqInfo *out) {
+    if (!data || !out) return -EINVAL;
+    av1::SeqHdr s;
+    const int r = av1::Decoder::find_seq_hdr(data, size, s);
+    if (r < 0) return r;
+    out->profile = s.profile;
+    out->max_w = s.max_width;
+    out->max_h = s.max_height;
+    out->bpc = s.bpc;
+    out->layout = s.layout;
+    out->film_grain_present = s.film_grain_present;
+    out->color = av1::color_info(s);
+    return 0;
 }
 
 }  // extern "C"

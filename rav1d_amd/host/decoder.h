@@ -19,6 +19,8 @@ namespace av1 {
 // motion state for later frames: decode.rs submit_frame / refs[]).
 struct FrameJob;
 
+inline MiColorInfo color_info(const SeqHdr &s) { return MiColorInfo{s.pri, s.trc, s.mtrx, s.color_range, s.chr}; }
+
 struct RefSlot {
     int pic_id = -1;
     // set while the frame that refreshed this slot is still being decoded on a worker thread:
@@ -50,6 +52,7 @@ struct DecEvent {
     // layer ids of the shown picture's frame (show_pic >= 0; else of `work`'s frame), and whether
     // that frame was the first its temporal unit decoded
     int temporal_id = 0, spatial_id = 0, new_tu = 0;
+    MiColorInfo color{};             // colour description of that frame's sequence header
 };
 
 // A picture on its way out (c.out / c.cache of the reference: src/lib.rs output_picture_ready).
@@ -58,6 +61,7 @@ struct ShownPic {
     MiFilmGrainData fg{};
     int fg_present = 0, mtrx_identity = 0;
     int temporal_id = 0, spatial_id = 0, new_tu = 0;
+    MiColorInfo color{};
 };
 
 class Decoder {
@@ -81,10 +85,13 @@ public:
     void drain();
     ~Decoder();
     std::string error;
+    // dav1d_parse_sequence_header (src/lib.rs): the first sequence header among the OBUs of
+    // `data`, parsed by parse_seq_hdr; 0, -ENOENT (none) or -EINVAL (malformed)
+    static int find_seq_hdr(const uint8_t *data, size_t size, SeqHdr &s);
 
 private:
     int parse_obu(const uint8_t *data, size_t size, size_t *used);
-    int parse_seq_hdr(Bits &gb, SeqHdr &s);
+    static int parse_seq_hdr(Bits &gb, SeqHdr &s);
     int parse_frame_hdr(Bits &gb, FrameHdr &h);
     int read_frame_size(Bits &gb, FrameHdr &h, bool use_ref);
     int submit_frame();

@@ -714,6 +714,32 @@ int Decoder::parse_frame_hdr(Bits &gb, FrameHdr &h) {
     return gb.error ? -EINVAL : 0;
 }
 
+// The OBU framing of parse_obu, looking for a sequence header only (lib.rs
+// dav1d_parse_sequence_header: every other OBU is skipped, the first sequence header wins).
+int Decoder::find_seq_hdr(const uint8_t *data, size_t size, SeqHdr &s) {
+    while (size) {
+        Bits gb;
+        gb.init(data, size);
+        gb.bit();   // forbidden
+        const int type = gb.bits(4);
+        const int has_ext = gb.bit(), has_len = gb.bit();
+        gb.bit();
+        if (has_ext) gb.bits(8);
+        const size_t len = has_len ? gb.uleb128() : size - 1 - has_ext;
+        if (gb.error) return -EINVAL;
+        const size_t hdr_bytes = gb.byte_pos();
+        if (len > size - hdr_bytes) return -EINVAL;
+        if (type == 1) {
+            Bits b;
+            b.init(data + hdr_bytes, len);
+            return parse_seq_hdr(b, s);
+        }
+        data += hdr_bytes + len;
+        size -= hdr_bytes + len;
+    }
+    return -ENOENT;
+}
+
 // Parse one OBU at data (size bytes available); *used = its total length.
 int Decoder::parse_obu(const uint8_t *data, size_t size, size_t *used) {
     Bits gb;
@@ -813,6 +839,7 @@ int Decoder::parse_obu(const uint8_t *data, size_t size, size_t *used) {
             sp.fg_present = rs.hdr->fg.present;
             sp.fg = rs.hdr->fg.data;
             sp.mtrx_identity = seq_->mtrx == 0;
+            sp.color = color_info(*seq_);
             sp.temporal_id = rs.hdr->temporal_id;
             sp.spatial_id = rs.hdr->spatial_id;
             sp.new_tu = rs.new_tu;
@@ -928,6 +955,7 @@ static void put(DecEvent &ev, const ShownPic &s) {
     ev.fg_present = s.fg_present;
     ev.fg = s.fg;
     ev.mtrx_identity = s.mtrx_identity;
+    ev.color = s.color;
     ev.temporal_id = s.temporal_id;
     ev.spatial_id = s.spatial_id;
     ev.new_tu = s.new_tu;
@@ -1266,6 +1294,7 @@ int Decoder::submit_frame() {
     ev.temporal_id = h.temporal_id;
     ev.spatial_id = h.spatial_id;
     ev.new_tu = new_tu;
+    ev.color = color_info(s);
     int ended = -1;
     if (h.show_frame) {
         ShownPic sp;
@@ -1273,6 +1302,7 @@ int Decoder::submit_frame() {
         sp.fg_present = h.fg.present;
         sp.fg = h.fg.data;
         sp.mtrx_identity = s.mtrx == 0;
+        sp.color = color_info(s);
         sp.temporal_id = h.temporal_id;
         sp.spatial_id = h.spatial_id;
         sp.new_tu = new_tu;

@@ -86,6 +86,55 @@ def decode_ivf(ctx, data, stream=None, sync_each=True, inloop_filters=14, thread
     frame_end(ctx, stream)
 
 
+def decode_to_tensors(ctx, data, format="nv12", apply_grain=True, matrix=None, stream=None, inloop_filters=14,
+                      threads=1, operating_point=0, all_layers=True, decode_frame_type="all", frame_size_limit=0):
+    """Decode a stream (IVF, Annex B or section 5) on the device and yield, per shown picture in
+    output order, (DisplayImage, MiColorInfo): the picture as a tight device tensor in `format`
+    ("nv12": semi-planar at the stream's own subsampling and bit depth; "rgb": planar R'G'B';
+    "rgba": packed with alpha; rav1d_amd.display.DisplayImage) through mi_display_picture, with
+    film grain when the frame carries it and apply_grain is set, and the colour description of
+    its sequence header. Every image is a fresh allocation the caller owns; its frame has been
+    checked with mi_frame_end before the conversion is enqueued, and the conversion has been
+    enqueued on `stream` (synchronise it, or stay on it, before reading).
+
+    matrix: the Dav1dMatrixCoefficients value the RGB formats convert with; an explicit value
+    overrides the stream's. With matrix=None the stream's own mtrx is used, and a stream that
+    leaves it unspecified (mtrx 2) gets BT.709 (1) when w >= 1280 or h > 576 and BT.601 (6)
+    otherwise, the usual rule for untagged video. The MiColorInfo yielded carries the matrix that
+    was used. The other settings are decode_ivf's."""
+    from .av1dec import MiColorInfo
+    from .display import FORMATS, OUT_SEMIPLANAR, DisplayImage, display_picture
+    fmt = FORMATS[format] if isinstance(format, str) else int(format)
+    dec = Av1Decoder(threads, inloop_filters, operating_point, all_layers, decode_frame_type, frame_size_limit)
+    pics = {}
+
+    def consume():
+        for ev in dec.events():
+            if ev.frame:
+                pics[ev.pic_id] = run_frame(ctx, ev.frame.contents, stream, _refs(pics, ev))
+                frame_end(ctx, stream)
+            if ev.show_pic >= 0:
+                src = pics[ev.show_pic].output()
+                color = MiColorInfo(*ev.color.astuple())
+                if fmt != OUT_SEMIPLANAR:
+                    if matrix is not None:
+                        color.mtrx = int(matrix)
+                    elif color.mtrx == 2:
+                        color.mtrx = 1 if (src.w >= 1280 or src.h > 576) else 6
+                image = DisplayImage(src.w, src.h, src.bpc, src.layout, fmt)
+                display_picture(ctx, src, image, color, ev.fg if (ev.fg_present and apply_grain) else None, stream)
+                yield image, color
+            for i in range(ev.n_release):
+                pics.pop(ev.release[i], None)
+
+    for tu in stream_units(data):
+        dec.send(tu)
+        yield from consume()
+    dec.drain()
+    yield from consume()
+    frame_end(ctx, stream)
+
+
 _extra_lanes = {}
 
 
