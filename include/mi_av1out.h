@@ -4,7 +4,7 @@
  *
  * Two libraries implement it:
  *   - librav1d_amd.so (gfx950): mi_host_picture_alloc / _free, mi_output_picture, and the
- *     display output that stays on the device, mi_display_picture;
+ *     output that stays on the device, mi_display_picture and mi_display_tensor;
  *   - libmi_av1dec.so (host C++): the muxers mi_muxer_* (no GPU code).
  *
  * Reference: the CLI's output stage (tools/output/output.rs), its muxers md5
@@ -121,6 +121,54 @@ typedef struct MiDisplayImage {
  * 10-14; -ENOMEM, -EIO. */
 int mi_display_picture(MiCtx *ctx, const MiPicture *in, const MiDisplayImage *out,
                        const MiColorInfo *color, const MiFilmGrainData *fg, void *stream);
+
+/* ---- device tensor output (librav1d_amd.so) ---------------------------------------------- */
+
+/* A shown picture as the tensor an ML consumer on the device reads: cropped, resized, normalised
+ * R'G'B', 3 channels (R, G, B) of w x h elements, in one pass over the decoded planes.
+ *
+ * The result is finish(resize(crop(P))), P the w x h picture MI_OUT_RGB_PLANAR gives for the same
+ * `in`, `color` and `fg` (the same chroma upsampler over the whole picture, the same matrix, the
+ * same colour rules, film grain through the same scratch picture), M = 2^bpc - 1.
+ *
+ * crop: crop_w x crop_h luma pixels of P at (crop_x, crop_y), inside the picture and at least
+ *   1 x 1; crop_w == 0 and crop_h == 0 take the whole picture (crop_x, crop_y are not read then).
+ *   The crop never changes a sample's value: odd origins are fine in 4:2:0.
+ * resize: separable, the horizontal pass first, its result an integer in [0, M] the vertical pass
+ *   runs over. Per axis (n_in the crop extent, n_out the output extent, S = 18), in exact integers:
+ *     Rr = 2 max(n_in, n_out); for output o, C = (2o+1) n_in; for every integer i
+ *     wt_i = Rr - |C - (2i+1) n_out|; the taps are the i with wt_i > 0 (a triangle filter on
+ *     half-pixel centres, widened by the downscale ratio; plain bilinear when n_in <= n_out);
+ *     W = sum wt_i, k_i = (wt_i 2^S + W/2) / W (floor); 2^S - sum k_i is added to the first tap
+ *     with the largest wt_i; tap i reads crop sample clamp(i, 0, n_in - 1);
+ *     out[o] = (sum k_i x_i + 2^(S-1)) >> S.
+ *   n_in == n_out is the identity. A downscale above 64:1 on either axis (n_in > 64 n_out) is
+ *   -EINVAL.
+ * finish, v the integer result:
+ *   MI_T_U8: v at 8 bpc, else min(255, (v + 2^(bpc-9)) >> (bpc-8)); scale and bias are not read;
+ *   float dtypes: f = fl32(fl32(float(v) * scale[c]) + bias[c]), two separately rounded float32
+ *   operations; MI_T_F32 stores f, MI_T_F16 / MI_T_BF16 store f rounded to nearest-even.
+ * destination: element (c, y, x) is at data + c stride[0] + y stride[1] + x stride[2]; only the
+ *   3 w h elements are written. Column stride == element size (CHW) and channel stride == element
+ *   size with a column stride of 3 elements (HWC) are the fast orders, so a slice of an NCHW or
+ *   channels-last batch is one of them; any other strides are stored element by element. */
+enum { MI_T_U8 = 0, MI_T_F16 = 1, MI_T_BF16 = 2, MI_T_F32 = 3 };
+typedef struct MiTensorImage {
+    void *data; ptrdiff_t stride[3];     /* bytes between channels, rows, columns */
+    int32_t w, h, dtype;                 /* output size; 3 channels, R, G, B */
+    int32_t crop_x, crop_y, crop_w, crop_h;  /* luma pixels of `in`; crop_w == 0 and crop_h == 0: the whole picture */
+    float scale[3], bias[3];             /* float dtypes: out = fl(fl(float(v) * scale[c]) + bias[c]) */
+} MiTensorImage;
+
+/* Enqueue the tensor output of `in` on `stream` (never synchronises); the context owns the
+ * scratch between the two passes (allocated on first use, replaced only when a call needs more).
+ * Every check precedes any device work: -EINVAL for a null or malformed argument, w or h outside
+ * 1..65536, an unknown dtype, a stride that is not a positive multiple of the element size, a
+ * `data` not aligned to it, a crop outside the picture or of zero extent, a downscale above 64:1,
+ * a non-finite scale or bias (float dtypes), NULL `color`, mtrx 2 or reserved, a bad range,
+ * identity without 4:4:4; -ENOTSUP for matrices 8 and 10-14; -ENOMEM and -EIO as above. */
+int mi_display_tensor(MiCtx *ctx, const MiPicture *in, const MiTensorImage *out,
+                      const MiColorInfo *color, const MiFilmGrainData *fg, void *stream);
 
 #ifdef __cplusplus
 }

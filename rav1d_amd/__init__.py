@@ -223,6 +223,9 @@ def lib():
     # (MiDisplayImage: rav1d_amd/display.py; MiColorInfo: rav1d_amd/av1dec.py)
     _sig(L, "mi_display_picture", ctypes.c_int, [_VP, ctypes.POINTER(MiPicture), _VP, _VP,
                                                  ctypes.POINTER(MiFilmGrainData), _VP])
+    # (MiTensorImage: rav1d_amd/display.py)
+    _sig(L, "mi_display_tensor", ctypes.c_int, [_VP, ctypes.POINTER(MiPicture), _VP, _VP,
+                                                ctypes.POINTER(MiFilmGrainData), _VP])
     _lib = L
     return L
 
@@ -239,7 +242,8 @@ EXPORTED = ["mi_version", "mi_ctx_create", "mi_ctx_destroy", "mi_ctx_last_error"
             "mi_dsp_mc_blend_v", "mi_dsp_mc_blend_h", "mi_dsp_mc_emu_edge", "mi_dsp_mc_warp8x8", "mi_dsp_mc_resize",
             "mi_dsp_mc_scaled", "mi_dsp_lr_wiener", "mi_dsp_lr_sgr",
             "mi_dsp_fg_generate_grain_y", "mi_dsp_fg_generate_grain_uv", "mi_dsp_fgy_32x32xn", "mi_dsp_fguv_32x32xn",
-            "mi_host_picture_alloc", "mi_host_picture_free", "mi_output_picture", "mi_display_picture"]
+            "mi_host_picture_alloc", "mi_host_picture_free", "mi_output_picture", "mi_display_picture",
+            "mi_display_tensor"]
 
 
 def check(rc, what):

@@ -507,6 +507,30 @@ struct DisplayArgs {
 };
 int launch_display(const DisplayArgs &a, int bpc, int format, hipStream_t s);
 
+// tensor output (tensor.hip): crop, separable triangle resize in 18-bit integers, finish to
+// u8 / f16 / bf16 / f32, of the R'G'B' picture DisplayArgs `d` describes (its source half only).
+// Scratch: `tab` holds per axis the first tap, the tap count and the taps (tap j of output o at
+// [j * n_out + o]); `mid` holds the horizontal pass's result, 3 x crop_h rows of mstride u16.
+constexpr int kTensorS = 18;      // fraction bits of a tap
+constexpr int kTensorSeg = 2048;  // source columns one workgroup of the horizontal pass holds
+struct TensorArgs {
+    DisplayArgs d;
+    int cx, cy, cw, ch;           // the crop, luma pixels
+    int ow, oh;                   // output size
+    int *tab;                     // hstart[ow] hcount[ow] hk[th][ow] vstart[oh] vcount[oh] vk[tv][oh]
+    int th, tv;                   // tap capacity per axis
+    uint16_t *mid;
+    int64_t mstride;              // u16 per row of mid, a multiple of 8
+    int u0, units, ob, segs;      // horizontal pass: first row unit, row units, outputs per segment, segments
+    int xblocks;                  // vertical pass: workgroups per output row
+    uint8_t *dst;
+    int64_t dstride[3];           // bytes between channels, rows, columns
+    int dtype, vec, shift;        // MI_T_*; whole-vector stores allowed; u8: bpc - 8
+    float scale[3], bias[3];
+};
+enum { kTensorCHW = 0, kTensorHWC = 1, kTensorAny = 2 };
+int launch_tensor(const TensorArgs &t, int bpc, int order, bool taps, hipStream_t s);
+
 // ---- per-call (table-compatible) entry points: single-block kernels ----
 struct LfCallArgs {
     uint8_t *dst;

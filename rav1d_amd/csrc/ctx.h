@@ -17,6 +17,11 @@ struct MiCtx {
     // the geometry of the shown picture, replaced only when a picture needs more)
     uint8_t *disp_fg = nullptr;
     size_t disp_fg_bytes = 0;
+    // mi_display_tensor: the tap tables and the horizontal pass's result (one allocation,
+    // replaced only when a call needs more)
+    uint8_t *tens = nullptr;
+    size_t tens_bytes = 0;
+    int tens_geom[4] = {0, 0, 0, 0};   // crop w, out w, crop h, out h of the tap tables it holds (0: none)
     // persistent intra reconstruction: per-block done epochs, queue heads, error word
     uint32_t *ir_done = nullptr;
     size_t ir_done_n = 0;
@@ -74,6 +79,7 @@ struct MiCtx {
         if (fg_scaling) (void)hipFree(fg_scaling);
         if (fg_offsets) (void)hipFree(fg_offsets);
         if (disp_fg) (void)hipFree(disp_fg);
+        if (tens) (void)hipFree(tens);
     }
 };
 

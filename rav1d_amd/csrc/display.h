@@ -1,0 +1,140 @@
+// display.h — what display.hip (mi_display_picture) and tensor.hip (mi_display_tensor) share: the
+// host side of the R'G'B' conversion (colour checks and 14-bit coefficients, the grained scratch
+// picture, the source half of DisplayArgs) and its device side (vector loads of a plane run, the
+// integer chroma upsampler, the matrix), so both entries compute the same picture.
+#pragma once
+#include "mi_av1out.h"
+#include "ctx.h"
+
+namespace mi {
+
+constexpr int kDispS = 14;   // fixed-point fraction bits of the matrix
+
+// ---- host (display.hip) ----
+// The colour rules of the RGB formats: -EINVAL for NULL `color`, mtrx 2 or reserved, a range that
+// is not 0 / 1, identity without 4:4:4; -ENOTSUP for matrices 8 and 10-14; else 0 with a.identity
+// or a.yo / a.ky / a.crv / a.cbu / a.cgu / a.cgv set. No device work.
+int display_color(const MiPicture *in, const MiColorInfo *color, DisplayArgs &a);
+// Point `src` (a copy of `in`) at the context's grained scratch picture in the geometry of `in`,
+// allocating or growing it: 0 or -ENOMEM (with last_error set). No launch.
+int display_grain_picture(MiCtx *ctx, const MiPicture *in, MiPicture *src);
+// The source half of DisplayArgs: planes, strides, vector-load flags, sizes, siting, H and M.
+void display_source(const MiPicture &src, const MiColorInfo *color, DisplayArgs &a);
+
+// ---- device ----
+
+// N samples of a plane row from column x0, columns clamped to pw - 1
+template <typename Px, int N>
+__device__ __forceinline__ void load_run(const uint8_t *row, int x0, int pw, bool vec, int (&v)[N]) {
+    const Px *p = reinterpret_cast<const Px *>(row);
+    constexpr int kBytes = N * (int)sizeof(Px);
+    static_assert(kBytes == 4 || kBytes == 8 || kBytes == 16, "one vector per run");
+    if (vec && x0 + N <= pw) {
+        uint32_t q[kBytes / 4];
+        if constexpr (kBytes == 16) {
+            const uint4 t = *reinterpret_cast<const uint4 *>(p + x0);
+            q[0] = t.x; q[1] = t.y; q[2] = t.z; q[3] = t.w;
+        } else if constexpr (kBytes == 8) {
+            const uint2 t = *reinterpret_cast<const uint2 *>(p + x0);
+            q[0] = t.x; q[1] = t.y;
+        } else {
+            q[0] = *reinterpret_cast<const uint32_t *>(p + x0);
+        }
+#pragma unroll
+        for (int k = 0; k < N; k++)
+            v[k] = sizeof(Px) == 1 ? (int)((q[k >> 2] >> (8 * (k & 3))) & 0xff) : (int)((q[k >> 1] >> (16 * (k & 1))) & 0xffff);
+    } else {
+#pragma unroll
+        for (int k = 0; k < N; k++) v[k] = (int)p[min(x0 + k, pw - 1)];
+    }
+}
+
+// chroma columns cx0 .. cx0 + 3 of one row and, in `halo`, column cx0 + 4 (the right neighbour
+// of the last odd luma column)
+template <typename Px>
+__device__ __forceinline__ void load5(const uint8_t *row, int cx0, int cw, bool vec, int (&v)[4], int &halo) {
+    load_run<Px, 4>(row, cx0, cw, vec, v);
+    halo = (int)reinterpret_cast<const Px *>(row)[min(cx0 + 4, cw - 1)];
+}
+
+// the vertical pass of 4:2:0 for one column: c = row j, cp = row max(j-1, 0), cn = row min(j+1, ch-1)
+__device__ __forceinline__ void vert420(bool coloc, int cp, int c, int cn, int &even, int &odd) {
+    even = coloc ? c : (cp + 3 * c + 2) >> 2;
+    odd = coloc ? (c + cn + 1) >> 1 : (3 * c + cn + 2) >> 2;
+}
+
+// the horizontal pass over 4 columns and their halo
+__device__ __forceinline__ void horz(const int (&v)[4], int halo, int (&o)[8]) {
+    o[0] = v[0]; o[1] = (v[0] + v[1] + 1) >> 1;
+    o[2] = v[1]; o[3] = (v[1] + v[2] + 1) >> 1;
+    o[4] = v[2]; o[5] = (v[2] + v[3] + 1) >> 1;
+    o[6] = v[3]; o[7] = (v[3] + halo + 1) >> 1;
+}
+
+// chroma plane p at luma resolution for the lane's 8 columns of row unit u: up[r] = luma row
+// u * (1 + ss_ver) + r. The vertical pass gives integer rows, the horizontal pass runs over them.
+template <typename Px>
+__device__ __forceinline__ void upsample(const DisplayArgs &a, int p, int u, int x0, int (&up)[2][8]) {
+    const uint8_t *base = a.src[p];
+    const int64_t st = a.sstride[1];
+    const bool vec = (a.svec >> p) & 1;
+    int t0[8], t1[8];   // (both rows are always set, and stored to `up` in one place, so that
+                        // they stay in registers; t1 is used by 4:2:0 only)
+    if (!a.ss_hor) {   // 4:4:4
+        load_run<Px, 8>(base + u * st, x0, a.cw, vec, t0);
+#pragma unroll
+        for (int k = 0; k < 8; k++) t1[k] = t0[k];
+    } else {
+        const int cx0 = x0 >> 1;
+        int c[4], hc, e[4], he, o[4], ho;
+        load5<Px>(base + u * st, cx0, a.cw, vec, c, hc);
+        if (!a.ss_ver) {   // 4:2:2
+#pragma unroll
+            for (int k = 0; k < 4; k++) e[k] = o[k] = c[k];
+            he = ho = hc;
+        } else {
+            int cn[4], hn, cp[4], hp;
+            load5<Px>(base + min(u + 1, a.ch - 1) * st, cx0, a.cw, vec, cn, hn);
+            // (co-located: the row above is not needed; re-reading row u keeps one code path)
+            load5<Px>(base + (a.coloc ? u : max(u - 1, 0)) * st, cx0, a.cw, vec, cp, hp);
+#pragma unroll
+            for (int k = 0; k < 4; k++) vert420(a.coloc, cp[k], c[k], cn[k], e[k], o[k]);
+            vert420(a.coloc, hp, hc, hn, he, ho);
+        }
+        horz(e, he, t0);
+        horz(o, ho, t1);
+    }
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        up[0][k] = t0[k];
+        up[1][k] = t1[k];
+    }
+}
+
+// 8 pixels (luma and chroma at luma resolution) to R'G'B'
+__device__ __forceinline__ void convert_run(const DisplayArgs &a, const int (&y)[8], const int (&cu)[8],
+                                            const int (&cv)[8], int (&R)[8], int (&G)[8], int (&B)[8]) {
+    constexpr int kRound = 1 << (kDispS - 1);
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        if (a.identity) {
+            G[k] = y[k];
+            B[k] = cu[k];
+            R[k] = cv[k];
+        } else {
+            const int l = a.ky * (y[k] - a.yo) + kRound;
+            int rr = l, gg = l, bb = l;
+            if (!a.mono) {
+                const int cb = cu[k] - a.half, cr = cv[k] - a.half;
+                rr += a.crv * cr;
+                gg -= a.cgu * cb + a.cgv * cr;
+                bb += a.cbu * cb;
+            }
+            R[k] = min(max(rr >> kDispS, 0), a.maxv);
+            G[k] = min(max(gg >> kDispS, 0), a.maxv);
+            B[k] = min(max(bb >> kDispS, 0), a.maxv);
+        }
+    }
+}
+
+}  // namespace mi

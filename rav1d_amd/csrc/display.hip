@@ -16,39 +16,10 @@
 #include <cmath>
 #include <cstring>
 
-#include "mi_av1out.h"
-#include "ctx.h"
+#include "display.h"
 
 namespace mi {
 namespace {
-
-constexpr int kDispS = 14;   // fixed-point fraction bits of the matrix
-
-// N samples of a plane row from column x0, columns clamped to pw - 1
-template <typename Px, int N>
-__device__ __forceinline__ void load_run(const uint8_t *row, int x0, int pw, bool vec, int (&v)[N]) {
-    const Px *p = reinterpret_cast<const Px *>(row);
-    constexpr int kBytes = N * (int)sizeof(Px);
-    static_assert(kBytes == 4 || kBytes == 8 || kBytes == 16, "one vector per run");
-    if (vec && x0 + N <= pw) {
-        uint32_t q[kBytes / 4];
-        if constexpr (kBytes == 16) {
-            const uint4 t = *reinterpret_cast<const uint4 *>(p + x0);
-            q[0] = t.x; q[1] = t.y; q[2] = t.z; q[3] = t.w;
-        } else if constexpr (kBytes == 8) {
-            const uint2 t = *reinterpret_cast<const uint2 *>(p + x0);
-            q[0] = t.x; q[1] = t.y;
-        } else {
-            q[0] = *reinterpret_cast<const uint32_t *>(p + x0);
-        }
-#pragma unroll
-        for (int k = 0; k < N; k++)
-            v[k] = sizeof(Px) == 1 ? (int)((q[k >> 2] >> (8 * (k & 3))) & 0xff) : (int)((q[k >> 1] >> (16 * (k & 1))) & 0xffff);
-    } else {
-#pragma unroll
-        for (int k = 0; k < N; k++) v[k] = (int)p[min(x0 + k, pw - 1)];
-    }
-}
 
 // N samples to a destination row at sample s0; the row holds `limit` samples
 template <typename Px, int N>
@@ -80,94 +51,12 @@ __device__ __forceinline__ void store_run(uint8_t *row, int s0, int limit, bool 
     }
 }
 
-// chroma columns cx0 .. cx0 + 3 of one row and, in `halo`, column cx0 + 4 (the right neighbour
-// of the last odd luma column)
-template <typename Px>
-__device__ __forceinline__ void load5(const uint8_t *row, int cx0, int cw, bool vec, int (&v)[4], int &halo) {
-    load_run<Px, 4>(row, cx0, cw, vec, v);
-    halo = (int)reinterpret_cast<const Px *>(row)[min(cx0 + 4, cw - 1)];
-}
-
-// the vertical pass of 4:2:0 for one column: c = row j, cp = row max(j-1, 0), cn = row min(j+1, ch-1)
-__device__ __forceinline__ void vert420(bool coloc, int cp, int c, int cn, int &even, int &odd) {
-    even = coloc ? c : (cp + 3 * c + 2) >> 2;
-    odd = coloc ? (c + cn + 1) >> 1 : (3 * c + cn + 2) >> 2;
-}
-
-// the horizontal pass over 4 columns and their halo
-__device__ __forceinline__ void horz(const int (&v)[4], int halo, int (&o)[8]) {
-    o[0] = v[0]; o[1] = (v[0] + v[1] + 1) >> 1;
-    o[2] = v[1]; o[3] = (v[1] + v[2] + 1) >> 1;
-    o[4] = v[2]; o[5] = (v[2] + v[3] + 1) >> 1;
-    o[6] = v[3]; o[7] = (v[3] + halo + 1) >> 1;
-}
-
-// chroma plane p at luma resolution for the lane's 8 columns of row unit u: up[r] = luma row
-// u * (1 + ss_ver) + r. The vertical pass gives integer rows, the horizontal pass runs over them.
-template <typename Px>
-__device__ __forceinline__ void upsample(const DisplayArgs &a, int p, int u, int x0, int (&up)[2][8]) {
-    const uint8_t *base = a.src[p];
-    const int64_t st = a.sstride[1];
-    const bool vec = (a.svec >> p) & 1;
-    int t0[8], t1[8];   // (both rows are always set, and stored to `up` in one place, so that
-                        // they stay in registers; t1 is used by 4:2:0 only)
-    if (!a.ss_hor) {   // 4:4:4
-        load_run<Px, 8>(base + u * st, x0, a.cw, vec, t0);
-#pragma unroll
-        for (int k = 0; k < 8; k++) t1[k] = t0[k];
-    } else {
-        const int cx0 = x0 >> 1;
-        int c[4], hc, e[4], he, o[4], ho;
-        load5<Px>(base + u * st, cx0, a.cw, vec, c, hc);
-        if (!a.ss_ver) {   // 4:2:2
-#pragma unroll
-            for (int k = 0; k < 4; k++) e[k] = o[k] = c[k];
-            he = ho = hc;
-        } else {
-            int cn[4], hn, cp[4], hp;
-            load5<Px>(base + min(u + 1, a.ch - 1) * st, cx0, a.cw, vec, cn, hn);
-            // (co-located: the row above is not needed; re-reading row u keeps one code path)
-            load5<Px>(base + (a.coloc ? u : max(u - 1, 0)) * st, cx0, a.cw, vec, cp, hp);
-#pragma unroll
-            for (int k = 0; k < 4; k++) vert420(a.coloc, cp[k], c[k], cn[k], e[k], o[k]);
-            vert420(a.coloc, hp, hc, hn, he, ho);
-        }
-        horz(e, he, t0);
-        horz(o, ho, t1);
-    }
-#pragma unroll
-    for (int k = 0; k < 8; k++) {
-        up[0][k] = t0[k];
-        up[1][k] = t1[k];
-    }
-}
-
 // 8 pixels of luma row `row` to R'G'B'
 template <typename Px, int FMT>
 __device__ __forceinline__ void rgb_row(const DisplayArgs &a, int row, int x0, const int (&y)[8], const int (&cu)[8],
                                         const int (&cv)[8]) {
-    constexpr int kRound = 1 << (kDispS - 1);
     int R[8], G[8], B[8];
-#pragma unroll
-    for (int k = 0; k < 8; k++) {
-        if (a.identity) {
-            G[k] = y[k];
-            B[k] = cu[k];
-            R[k] = cv[k];
-        } else {
-            const int l = a.ky * (y[k] - a.yo) + kRound;
-            int rr = l, gg = l, bb = l;
-            if (!a.mono) {
-                const int cb = cu[k] - a.half, cr = cv[k] - a.half;
-                rr += a.crv * cr;
-                gg -= a.cgu * cb + a.cgv * cr;
-                bb += a.cbu * cb;
-            }
-            R[k] = min(max(rr >> kDispS, 0), a.maxv);
-            G[k] = min(max(gg >> kDispS, 0), a.maxv);
-            B[k] = min(max(bb >> kDispS, 0), a.maxv);
-        }
-    }
+    convert_run(a, y, cu, cv, R, G, B);
     if constexpr (FMT == MI_OUT_RGB_PLANAR) {
         store_run<Px, 8>(a.dst[0] + row * a.dstride[0], x0, a.w, a.dvec & 1, R);
         store_run<Px, 8>(a.dst[1] + row * a.dstride[1], x0, a.w, (a.dvec >> 1) & 1, G);
@@ -298,7 +187,6 @@ int launch_display(const DisplayArgs &a, int bpc, int format, hipStream_t s) {
     return bpc == 8 ? launch_px<uint8_t>(a, format, s) : launch_px<uint16_t>(a, format, s);
 }
 
-}  // namespace mi
 
 namespace {
 
@@ -317,11 +205,73 @@ int matrix_k(int mtrx, double *kr, double *kb) {
     }
 }
 
-int round_fix(double v) { return (int)floor(v * (double)(1 << mi::kDispS) + 0.5); }
+int round_fix(double v) { return (int)floor(v * (double)(1 << kDispS) + 0.5); }
 
 bool aligned16(const void *p, ptrdiff_t stride) { return (((uintptr_t)p | (uintptr_t)stride) & 15) == 0; }
 
 }  // namespace
+
+int display_color(const MiPicture *in, const MiColorInfo *color, DisplayArgs &a) {
+    if (!color || color->mtrx == 2 || (color->range != 0 && color->range != 1)) return -EINVAL;
+    if (color->mtrx == 0) {
+        if (in->layout != 3) return -EINVAL;
+        a.identity = 1;
+        return 0;
+    }
+    double kr, kb;
+    if (int e = matrix_k(color->mtrx, &kr, &kb)) return e;
+    const int b = in->bpc;
+    const double m = (double)((1 << b) - 1), kg = 1.0 - kr - kb;
+    const double kc = color->range ? 1.0 : m / (double)(224 << (b - 8));
+    a.yo = color->range ? 0 : 16 << (b - 8);
+    a.ky = color->range ? 1 << kDispS : round_fix(m / (double)(219 << (b - 8)));
+    a.crv = round_fix(2.0 * (1.0 - kr) * kc);
+    a.cbu = round_fix(2.0 * (1.0 - kb) * kc);
+    a.cgu = round_fix(2.0 * kb * (1.0 - kb) / kg * kc);
+    a.cgv = round_fix(2.0 * kr * (1.0 - kr) / kg * kc);
+    return 0;
+}
+
+int display_grain_picture(MiCtx *ctx, const MiPicture *in, MiPicture *src) {
+    // the grained picture, in the geometry of `in`
+    const int ss_ver = in->layout == 1;
+    const size_t ah = ((size_t)in->h + 127) & ~(size_t)127;
+    const size_t ybytes = ((size_t)in->stride[0] * ah + 255) & ~(size_t)255;
+    const size_t cbytes = in->layout ? ((size_t)in->stride[1] * (ah >> ss_ver) + 255) & ~(size_t)255 : 0;
+    if (ybytes + 2 * cbytes > ctx->disp_fg_bytes) {
+        if (ctx->disp_fg) (void)hipFree(ctx->disp_fg);   // (waits for the work that reads it)
+        ctx->disp_fg = nullptr;
+        ctx->disp_fg_bytes = 0;
+        if (hipMalloc(&ctx->disp_fg, ybytes + 2 * cbytes) != hipSuccess) return ctx->last_error = -ENOMEM;
+        ctx->disp_fg_bytes = ybytes + 2 * cbytes;
+    }
+    src->data[0] = ctx->disp_fg;
+    src->data[1] = in->layout ? ctx->disp_fg + ybytes : nullptr;
+    src->data[2] = in->layout ? ctx->disp_fg + ybytes + cbytes : nullptr;
+    return 0;
+}
+
+void display_source(const MiPicture &src, const MiColorInfo *color, DisplayArgs &a) {
+    const int ss_hor = src.layout == 1 || src.layout == 2, ss_ver = src.layout == 1;
+    for (int p = 0; p < (src.layout ? 3 : 1); p++) {
+        a.src[p] = (const uint8_t *)src.data[p];
+        if (aligned16(src.data[p], src.stride[p ? 1 : 0])) a.svec |= 1 << p;
+    }
+    a.sstride[0] = src.stride[0];
+    a.sstride[1] = src.stride[1];
+    a.w = src.w;
+    a.h = src.h;
+    a.cw = (src.w + ss_hor) >> ss_hor;
+    a.ch = (src.h + ss_ver) >> ss_ver;
+    a.ss_hor = ss_hor;
+    a.ss_ver = ss_ver;
+    a.mono = src.layout == 0;
+    a.coloc = color && color->chr == 2;
+    a.half = 1 << (src.bpc - 1);
+    a.maxv = (1 << src.bpc) - 1;
+}
+
+}  // namespace mi
 
 extern "C" int mi_display_picture(MiCtx *ctx, const MiPicture *in, const MiDisplayImage *out, const MiColorInfo *color,
                                   const MiFilmGrainData *fg, void *stream) {
@@ -347,68 +297,23 @@ extern "C" int mi_display_picture(MiCtx *ctx, const MiPicture *in, const MiDispl
 
     mi::DisplayArgs a;
     memset(&a, 0, sizeof(a));
-    if (out->format != MI_OUT_SEMIPLANAR) {
-        if (!color || color->mtrx == 2 || (color->range != 0 && color->range != 1)) return -EINVAL;
-        if (color->mtrx == 0) {
-            if (in->layout != 3) return -EINVAL;
-            a.identity = 1;
-        } else {
-            double kr, kb;
-            if (int e = matrix_k(color->mtrx, &kr, &kb)) return e;
-            const int b = in->bpc;
-            const double m = (double)((1 << b) - 1), kg = 1.0 - kr - kb;
-            const double kc = color->range ? 1.0 : m / (double)(224 << (b - 8));
-            a.yo = color->range ? 0 : 16 << (b - 8);
-            a.ky = color->range ? 1 << mi::kDispS : round_fix(m / (double)(219 << (b - 8)));
-            a.crv = round_fix(2.0 * (1.0 - kr) * kc);
-            a.cbu = round_fix(2.0 * (1.0 - kb) * kc);
-            a.cgu = round_fix(2.0 * kb * (1.0 - kb) / kg * kc);
-            a.cgv = round_fix(2.0 * kr * (1.0 - kr) / kg * kc);
-        }
-    }
+    if (out->format != MI_OUT_SEMIPLANAR)
+        if (int e = mi::display_color(in, color, a)) return e;
     if (!ctx) return -EINVAL;
 
     MiPicture src = *in;
     if (fg) {
-        // the grained picture, in the geometry of `in`
-        const size_t ah = ((size_t)in->h + 127) & ~(size_t)127;
-        const size_t ybytes = ((size_t)in->stride[0] * ah + 255) & ~(size_t)255;
-        const size_t cbytes = in->layout ? ((size_t)in->stride[1] * (ah >> ss_ver) + 255) & ~(size_t)255 : 0;
-        if (ybytes + 2 * cbytes > ctx->disp_fg_bytes) {
-            if (ctx->disp_fg) (void)hipFree(ctx->disp_fg);   // (waits for the work that reads it)
-            ctx->disp_fg = nullptr;
-            ctx->disp_fg_bytes = 0;
-            if (hipMalloc(&ctx->disp_fg, ybytes + 2 * cbytes) != hipSuccess) return ctx->last_error = -ENOMEM;
-            ctx->disp_fg_bytes = ybytes + 2 * cbytes;
-        }
-        src.data[0] = ctx->disp_fg;
-        src.data[1] = in->layout ? ctx->disp_fg + ybytes : nullptr;
-        src.data[2] = in->layout ? ctx->disp_fg + ybytes + cbytes : nullptr;
+        if (int e = mi::display_grain_picture(ctx, in, &src)) return e;
         if (int e = mi_film_grain_frame(ctx, in, &src, fg, color && color->mtrx == 0, stream)) return e;
     }
 
-    for (int p = 0; p < (in->layout ? 3 : 1); p++) {
-        a.src[p] = (const uint8_t *)src.data[p];
-        if (aligned16(src.data[p], src.stride[p ? 1 : 0])) a.svec |= 1 << p;
-    }
-    a.sstride[0] = src.stride[0];
-    a.sstride[1] = src.stride[1];
+    mi::display_source(src, color, a);
     for (int p = 0; p < ndst; p++) {
         a.dst[p] = (uint8_t *)out->data[p];
         a.dstride[p] = out->stride[p];
-        if (aligned16(out->data[p], out->stride[p])) a.dvec |= 1 << p;
+        if (mi::aligned16(out->data[p], out->stride[p])) a.dvec |= 1 << p;
     }
-    a.w = in->w;
-    a.h = in->h;
-    a.cw = cw;
-    a.ch = ch;
-    a.ss_hor = ss_hor;
-    a.ss_ver = ss_ver;
-    a.mono = in->layout == 0;
-    a.coloc = color && color->chr == 2;
     a.shift = out->format == MI_OUT_SEMIPLANAR && in->bpc > 8 ? 16 - in->bpc : 0;
-    a.half = 1 << (in->bpc - 1);
-    a.maxv = (1 << in->bpc) - 1;
     a.chunks = (in->w + 7) >> 3;
     a.units = ss_ver ? ch : in->h;
     if (mi::launch_display(a, in->bpc, out->format, (hipStream_t)stream)) return ctx->last_error = -EIO;

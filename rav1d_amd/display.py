@@ -1,7 +1,8 @@
 """Device display output (include/mi_av1out.h, mi_display_picture): a shown picture as a tight
 torch tensor on the device, semi-planar YUV (NV12 / P010 and their 4:2:2 / 4:4:4 kin) or R'G'B'
 (planar, or packed with alpha), with film grain applied. torch allocates; the conversion is the
-gfx950 kernel of csrc/display.hip."""
+gfx950 kernel of csrc/display.hip. display_tensor (mi_display_tensor, csrc/tensor.hip) writes the
+cropped, resized, normalised R'G'B' tensor an ML consumer reads."""
 import ctypes
 
 import torch
@@ -91,5 +92,65 @@ def display_picture(ctx, frame, image, color=None, fg=None, stream=None):
           "mi_display_picture")
 
 
+T_U8, T_F16, T_BF16, T_F32 = 0, 1, 2, 3
+_TENSOR_DTYPES = {torch.uint8: T_U8, torch.float16: T_F16, torch.bfloat16: T_BF16, torch.float32: T_F32}
+
+
+class MiTensorImage(ctypes.Structure):
+    _fields_ = [("data", ctypes.c_void_p), ("stride", ctypes.c_ssize_t * 3),
+                ("w", ctypes.c_int32), ("h", ctypes.c_int32), ("dtype", ctypes.c_int32),
+                ("crop_x", ctypes.c_int32), ("crop_y", ctypes.c_int32), ("crop_w", ctypes.c_int32),
+                ("crop_h", ctypes.c_int32), ("scale", ctypes.c_float * 3), ("bias", ctypes.c_float * 3)]
+
+
+def tensor_image(out, bpc, crop=None, mean=None, std=None, channels_last=False):
+    """The MiTensorImage over `out`, a (3, H, W) tensor in any strides (or (H, W, 3) with
+    channels_last) of dtype uint8, float16, bfloat16 or float32, for a frame of `bpc` bits:
+    scale[c] = float32(1 / (M std[c])), bias[c] = float32(-mean[c] / std[c]), M = 2^bpc - 1,
+    computed in Python floats and rounded once. crop: (x, y, w, h) in luma pixels, or None."""
+    if out.dim() != 3 or out.shape[2 if channels_last else 0] != 3:
+        raise ValueError(f"out of shape {tuple(out.shape)}: want {'(H, W, 3)' if channels_last else '(3, H, W)'}")
+    if out.dtype not in _TENSOR_DTYPES:
+        raise ValueError(f"out of dtype {out.dtype}")
+    if channels_last:
+        out = out.permute(2, 0, 1)
+    im = MiTensorImage()
+    es = out.element_size()
+    im.data, im.dtype = out.data_ptr(), _TENSOR_DTYPES[out.dtype]
+    im.h, im.w = out.shape[1], out.shape[2]
+    for i in range(3):
+        # (a dimension of size 1 may carry any stride; none of its steps is ever taken)
+        im.stride[i] = out.stride(i) * es if out.shape[i] > 1 and out.stride(i) > 0 else es
+    if crop is not None:
+        im.crop_x, im.crop_y, im.crop_w, im.crop_h = (int(v) for v in crop)
+    mean = (0.0, 0.0, 0.0) if mean is None else tuple(float(v) for v in mean)
+    std = (1.0, 1.0, 1.0) if std is None else tuple(float(v) for v in std)
+    m = float((1 << bpc) - 1)
+    for c in range(3):
+        im.scale[c] = 1.0 / (m * std[c])
+        im.bias[c] = -mean[c] / std[c]
+    return im
+
+
+def display_tensor(ctx, frame, out, color, fg=None, crop=None, mean=None, std=None, stream=None, channels_last=False):
+    """Enqueue mi_display_tensor: `frame` (a device Frame or a MiPicture) cropped to `crop`
+    ((x, y, w, h) in luma pixels; None: the whole picture), resized to the size of `out` and
+    normalised, as R'G'B' into `out`: a device tensor of shape (3, H, W) in any strides (batch[n] of
+    an NCHW or a channels-last batch), or (H, W, 3) with channels_last; dtype and strides are the
+    tensor's. Float dtypes receive (v / M - mean[c]) / std[c] (defaults 0 and 1: [0, 1]), uint8
+    the sample at 8 bits. color: a MiColorInfo, as for display_picture's RGB formats; fg: film
+    grain. `out` may also be a ready MiTensorImage. Raises MiError on a negative return."""
+    from .frame import _stream_ptr, film_grain_data
+    src = frame if isinstance(frame, MiPicture) else frame.picture()
+    im = out if isinstance(out, MiTensorImage) else tensor_image(out, src.bpc, crop, mean, std, channels_last)
+    if fg is not None and not isinstance(fg, MiFilmGrainData):
+        fg = film_grain_data(fg)
+    check(lib().mi_display_tensor(ctx.h, ctypes.byref(src), ctypes.byref(im),
+                                  ctypes.byref(color) if color is not None else None,
+                                  ctypes.byref(fg) if fg is not None else None, _stream_ptr(stream)),
+          "mi_display_tensor")
+
+
 __all__ = ["DisplayImage", "MiDisplayImage", "MiColorInfo", "display_picture", "FORMATS",
-           "OUT_SEMIPLANAR", "OUT_RGB_PLANAR", "OUT_RGBA_PACKED"]
+           "OUT_SEMIPLANAR", "OUT_RGB_PLANAR", "OUT_RGBA_PACKED",
+           "MiTensorImage", "tensor_image", "display_tensor", "T_U8", "T_F16", "T_BF16", "T_F32"]

@@ -135,6 +135,90 @@ def decode_to_tensors(ctx, data, format="nv12", apply_grain=True, matrix=None, s
     frame_end(ctx, stream)
 
 
+def fit_crop(w, h, W, H, fit):
+    """The crop (x, y, cw, ch) of a w x h picture for a W x H target: "stretch" takes the whole
+    picture, "crop" the largest centred rectangle of the target's aspect."""
+    if fit == "stretch":
+        return 0, 0, w, h
+    if fit != "crop":
+        raise ValueError(f"fit {fit!r}")
+    if w * H >= h * W:
+        cw = max(1, (h * W) // H)
+        return (w - cw) // 2, 0, cw, h
+    ch = max(1, (w * H) // W)
+    return 0, (h - ch) // 2, w, ch
+
+
+def decode_to_batches(ctx, data, size, batch=8, dtype=None, channels_last=False, mean=None, std=None, fit="stretch",
+                      every=1, apply_grain=True, matrix=None, stream=None, inloop_filters=14, threads=1,
+                      operating_point=0, all_layers=True, decode_frame_type="all", frame_size_limit=0):
+    """Decode a stream on the device and yield (tensor, [MiColorInfo, ...]) batches for an ML
+    consumer: the tensor is (n, 3, H, W) with size = (W, H), n = batch except for a shorter last
+    one, of `dtype` (torch.float16 by default; bfloat16, float32 or uint8), contiguous or, with
+    channels_last, in torch.channels_last memory format. Every `every`-th shown picture (the
+    first, then each every-th after it) goes through mi_display_tensor (rav1d_amd.display
+    .display_tensor) into its slot: cropped per `fit` (fit_crop; pictures of different sizes in a
+    stream each get their own crop), resized, normalised with mean / std per channel, with film
+    grain when the frame carries it and apply_grain is set. The list holds the colour description
+    used for each slot; matrix follows decode_to_tensors's rule. Each tensor is a fresh allocation
+    the caller owns, filled by work enqueued on `stream` (synchronise it, or stay on it, before
+    reading). The other settings are decode_ivf's."""
+    import torch
+
+    from .av1dec import MiColorInfo
+    from .display import display_tensor
+    W, H = (int(v) for v in size)
+    if batch < 1 or every < 1:
+        raise ValueError("batch and every must be at least 1")
+    fit_crop(1, 1, W, H, fit)      # (an unknown fit fails before any decoding)
+    dtype = torch.float16 if dtype is None else dtype
+    dec = Av1Decoder(threads, inloop_filters, operating_point, all_layers, decode_frame_type, frame_size_limit)
+    pics = {}
+    state = dict(shown=0, tensor=None, colors=[])
+
+    def new_batch():
+        t = torch.empty((batch, 3, H, W), dtype=dtype, device="cuda",
+                        memory_format=torch.channels_last if channels_last else torch.contiguous_format)
+        state["tensor"], state["colors"] = t, []
+
+    def consume():
+        for ev in dec.events():
+            if ev.frame:
+                pics[ev.pic_id] = run_frame(ctx, ev.frame.contents, stream, _refs(pics, ev))
+                frame_end(ctx, stream)
+            if ev.show_pic >= 0:
+                take = state["shown"] % every == 0
+                state["shown"] += 1
+                if take:
+                    src = pics[ev.show_pic].output()
+                    color = MiColorInfo(*ev.color.astuple())
+                    if matrix is not None:
+                        color.mtrx = int(matrix)
+                    elif color.mtrx == 2:
+                        color.mtrx = 1 if (src.w >= 1280 or src.h > 576) else 6
+                    if state["tensor"] is None:
+                        new_batch()
+                    display_tensor(ctx, src, state["tensor"][len(state["colors"])], color,
+                                   ev.fg if (ev.fg_present and apply_grain) else None,
+                                   fit_crop(src.w, src.h, W, H, fit), mean, std, stream)
+                    state["colors"].append(color)
+                    if len(state["colors"]) == batch:
+                        out = state["tensor"], state["colors"]
+                        state["tensor"] = None
+                        yield out
+            for i in range(ev.n_release):
+                pics.pop(ev.release[i], None)
+
+    for tu in stream_units(data):
+        dec.send(tu)
+        yield from consume()
+    dec.drain()
+    yield from consume()
+    frame_end(ctx, stream)
+    if state["tensor"] is not None:
+        yield state["tensor"][:len(state["colors"])], state["colors"]
+
+
 _extra_lanes = {}
 
 
