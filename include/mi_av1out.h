@@ -104,7 +104,8 @@ void mi_muxer_close(MiMuxer *m);
  *   G = clip((ky (y-Yo) - cgu (u-H) - cgv (v-H) + 2^(S-1)) >> S, 0, M)
  *   B = clip((ky (y-Yo) + cbu (u-H) + 2^(S-1)) >> S, 0, M)
  * mtrx 0 (identity, 4:4:4 only): G = Y, B = U, R = V. 4:0:0: R = G = B from the luma term. No
- * transfer-function or primaries conversion: the output is R'G'B' in the stream's primaries. */
+ * transfer-function or primaries conversion: the output is R'G'B' in the stream's primaries
+ * (mi_display_picture_tm and mi_display_tensor_tm below add that stage). */
 enum { MI_OUT_SEMIPLANAR = 0, MI_OUT_RGB_PLANAR = 1, MI_OUT_RGBA_PACKED = 2 };
 typedef struct MiDisplayImage {
     void *data[3]; ptrdiff_t stride[3];   /* bytes; any device-accessible memory */
@@ -169,6 +170,78 @@ typedef struct MiTensorImage {
  * identity without 4:4:4; -ENOTSUP for matrices 8 and 10-14; -ENOMEM and -EIO as above. */
 int mi_display_tensor(MiCtx *ctx, const MiPicture *in, const MiTensorImage *out,
                       const MiColorInfo *color, const MiFilmGrainData *fg, void *stream);
+
+/* ---- colour-volume stage: tone mapping and gamut conversion (librav1d_amd.so) ------------ */
+
+/* An optional stage after the matrix, in the same pass: source-coded R'G'B' at the source depth
+ * (the integers the matrix gives, identity and 4:0:0 included, clipped to [0, Ms]) to
+ * destination-coded R'G'B' at dst_bpc. The source is described by color->pri and color->trc:
+ *   pri 1, 5, 6, 7, 9, 12 (H.273 chromaticities, D65 white (0.3127, 0.3290)); 2 (unspecified: the
+ *     caller has to choose, as for mtrx 2) and reserved values are -EINVAL, every other defined
+ *     value (4, 8, 10, 11, 22) -ENOTSUP;
+ *   trc 1, 6, 14, 15 (the BT.709 curve), 13 (sRGB), 16 (PQ, ST 2084); 2 and reserved values are
+ *     -EINVAL, every other defined value (4, 5, 7 - 12, 17, 18: HLG among them) -ENOTSUP.
+ * Ms = 2^src_bpc - 1, Md = 2^dst_bpc - 1. Three tables, built on the host in double precision and
+ * rounded once:
+ *   lut_in[v], v = 0 .. Ms, x = v / Ms: linear light in [0, 1] as float32.
+ *     BT.709 curve: x / 4.5 for x < 0.081, else ((x + 0.099) / 1.099)^(1 / 0.45);
+ *     sRGB: x / 12.92 for x <= 0.04045, else ((x + 0.055) / 1.055)^2.4;
+ *     PQ: m1 = 2610/16384, m2 = 2523/32, c1 = 3424/4096, c2 = 2413/128, c3 = 2392/128,
+ *       N(L) = ((c1 + c2 Y^m1) / (1 + c3 Y^m1))^m2 with Y = L / 10000 (the inverse EOTF of L nits),
+ *       EOTF(E) = 10000 (max(E^(1/m2) - c1, 0) / (c2 - c3 E^(1/m2)))^(1/m1) nits; the BT.2390 EETF
+ *       with black level 0, per channel on the R'G'B' signal: E1 = min(x / N(src_peak), 1),
+ *       maxLum = min(N(dst_peak) / N(src_peak), 1), KS = 1.5 maxLum - 0.5; E2 = E1 for E1 < KS (and
+ *       always when KS = 1), else with T = (E1 - KS) / (1 - KS)
+ *       E2 = (2T^3 - 3T^2 + 1) KS + (T^3 - 2T^2 + T)(1 - KS) + (-2T^3 + 3T^2) maxLum;
+ *       lut_in = min(EOTF(E2 N(src_peak)) / dst_peak, 1).
+ *     lut_in[0] is exactly 0, and every later entry is the largest value of the formula over the
+ *     codes 1 .. v (the table never decreases: the two segments of the BT.709 curve, with the
+ *     constants as the standard rounds them, meet 5.5e-5 apart at x = 0.081, more than a 12-bit
+ *     code's step); a value that would round to a subnormal float32 is 0.
+ *   m[9]: row-major float32 of inv(RGB->XYZ of dst_pri) (RGB->XYZ of color->pri); the exact
+ *     identity when the two are the same value.
+ *   lut_out[i], i = 0 .. 65535: floor(OETF(i / 65535) Md + 0.5) as uint16, L = i / 65535.
+ *     BT.709: 4.5 L for L < 0.018, else 1.099 L^0.45 - 0.099;
+ *     sRGB: 12.92 L for L <= 0.0031308, else 1.055 L^(1/2.4) - 0.055.
+ * Per pixel on the device, every float32 operation rounded separately (no fused multiply-add):
+ *   r = lut_in[R'], g = lut_in[G'], b = lut_in[B']; for each row k of m:
+ *   t = fl(fl(fl(m[k][0] r) + fl(m[k][1] g)) + fl(m[k][2] b)); t = min(max(t, 0), 1);
+ *   out_k = lut_out[(int)fl(fl(t * 65535) + 0.5)]   (the conversion truncates). */
+typedef struct MiToneMap {
+    int32_t dst_pri;    /* Dav1dColorPrimaries of the output: 1 (BT.709), 9 (BT.2020), 12 (P3-D65) */
+    int32_t dst_trc;    /* output OETF: 1 (BT.709) or 13 (sRGB) */
+    int32_t dst_bpc;    /* output depth: 8, 10 or 12, independent of the source depth */
+    float src_peak;     /* PQ sources: mastering peak Lw, nits */
+    float dst_peak;     /* PQ sources: target peak Lmax, nits; linear light is normalised by it */
+} MiToneMap;
+
+/* Host only, no device and no context: the tables the device stage uses for a source of
+ * `src_bpc` bits (8, 10, 12) described by color->pri and color->trc. lut_in receives
+ * 1 << src_bpc floats, m 9, lut_out 65536 entries. -EINVAL for a NULL argument, a dst_pri,
+ * dst_trc or dst_bpc outside the lists above, a src_bpc other than 8, 10, 12, pri or trc 2 or
+ * reserved, and for PQ sources a peak that is not finite or lies outside [1, 10000] (other sources
+ * do not read the peaks); -ENOTSUP for the other defined pri and trc values. */
+int mi_tonemap_tables(const MiToneMap *tm, const MiColorInfo *color, int src_bpc,
+                      float *lut_in, float m[9], uint16_t *lut_out);
+
+/* mi_display_picture with the colour-volume stage: the RGB formats only (MI_OUT_SEMIPLANAR is
+ * -ENOTSUP); out->bpc must equal tm->dst_bpc and need not equal in->bpc; the sample type follows
+ * out->bpc (u8 at 8, else u16 LSB-aligned) and alpha is 2^dst_bpc - 1. The checks of
+ * mi_display_picture (its colour-matrix rules included) and of mi_tonemap_tables apply, all before
+ * any device work, the NULL `ctx` last. The context owns the device tables: they are rebuilt and
+ * uploaded (on `stream`, without synchronising it) only when *tm, color->pri, color->trc or
+ * in->bpc differ from the call before; calls on one context use one stream, which orders a table
+ * change behind the kernels still reading the old tables. */
+int mi_display_picture_tm(MiCtx *ctx, const MiPicture *in, const MiDisplayImage *out,
+                          const MiColorInfo *color, const MiToneMap *tm,
+                          const MiFilmGrainData *fg, void *stream);
+
+/* mi_display_tensor with the colour-volume stage: the picture P of its definition is the
+ * tone-mapped picture (MI_OUT_RGB_PLANAR of mi_display_picture_tm) and M is 2^dst_bpc - 1 (so
+ * MI_T_U8 shifts by dst_bpc - 8); crop, resize and finish are otherwise as written there. */
+int mi_display_tensor_tm(MiCtx *ctx, const MiPicture *in, const MiTensorImage *out,
+                         const MiColorInfo *color, const MiToneMap *tm,
+                         const MiFilmGrainData *fg, void *stream);
 
 #ifdef __cplusplus
 }

@@ -507,6 +507,24 @@ struct DisplayArgs {
 };
 int launch_display(const DisplayArgs &a, int bpc, int format, hipStream_t s);
 
+// colour-volume stage of the RGB outputs (mi_display_picture_tm, mi_display_tensor_tm; host side
+// tonemap.cpp): after the matrix, per channel lut_in (source code -> linear light), the 3 x 3
+// primaries matrix, clip, lut_out (linear light in 16 bits -> destination code). A kernel
+// parameter of its own, passed only to the instantiations with the stage (ToneParam).
+struct ToneArgs {
+    const float *lut_in;          // 1 << source bpc entries
+    const uint16_t *lut_out;      // 65536 entries, values in [0, maxd]
+    float m[9];                   // row-major
+    int n_in;                     // 1 << source bpc
+    int maxd;                     // 2^dst_bpc - 1: alpha
+};
+struct NoTone {};
+template <bool TM> struct ToneSel { using type = NoTone; };
+template <> struct ToneSel<true> { using type = ToneArgs; };
+template <bool TM> using ToneParam = typename ToneSel<TM>::type;
+// RGB formats only; the destination samples are u8 at dst_bpc 8, else u16
+int launch_display_tm(const DisplayArgs &a, const ToneArgs &tm, int bpc, int dst_bpc, int format, hipStream_t s);
+
 // tensor output (tensor.hip): crop, separable triangle resize in 18-bit integers, finish to
 // u8 / f16 / bf16 / f32, of the R'G'B' picture DisplayArgs `d` describes (its source half only).
 // Scratch: `tab` holds per axis the first tap, the tap count and the taps (tap j of output o at
@@ -529,7 +547,8 @@ struct TensorArgs {
     float scale[3], bias[3];
 };
 enum { kTensorCHW = 0, kTensorHWC = 1, kTensorAny = 2 };
-int launch_tensor(const TensorArgs &t, int bpc, int order, bool taps, hipStream_t s);
+// tm: the colour-volume stage in the tile fill of the horizontal pass, or nullptr
+int launch_tensor(const TensorArgs &t, int bpc, int order, bool taps, hipStream_t s, const ToneArgs *tm = nullptr);
 
 // ---- per-call (table-compatible) entry points: single-block kernels ----
 struct LfCallArgs {

@@ -22,6 +22,17 @@ struct MiCtx {
     uint8_t *tens = nullptr;
     size_t tens_bytes = 0;
     int tens_geom[4] = {0, 0, 0, 0};   // crop w, out w, crop h, out h of the tap tables it holds (0: none)
+    // mi_display_*_tm: the device tables (lut_out, then lut_in) of the key `tone_key` (*tm with
+    // the peaks zeroed for sources that do not read them, pri, trc, source bpc), their matrix, and
+    // two pinned staging buffers used in turn; `tone_ev[i]` marks when buffer i may be rewritten
+    uint8_t *tone_dev = nullptr;
+    uint8_t *tone_host[2] = {nullptr, nullptr};
+    hipEvent_t tone_ev[2] = {nullptr, nullptr};
+    bool tone_ev_pending[2] = {false, false};
+    int tone_slot = 0;
+    bool tone_valid = false;
+    int32_t tone_key[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    float tone_m[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     // persistent intra reconstruction: per-block done epochs, queue heads, error word
     uint32_t *ir_done = nullptr;
     size_t ir_done_n = 0;
@@ -80,6 +91,11 @@ struct MiCtx {
         if (fg_offsets) (void)hipFree(fg_offsets);
         if (disp_fg) (void)hipFree(disp_fg);
         if (tens) (void)hipFree(tens);
+        if (tone_dev) (void)hipFree(tone_dev);
+        for (int i = 0; i < 2; i++) {
+            if (tone_ev[i]) (void)hipEventDestroy(tone_ev[i]);
+            if (tone_host[i]) (void)hipHostFree(tone_host[i]);
+        }
     }
 };
 

@@ -21,7 +21,52 @@ int display_grain_picture(MiCtx *ctx, const MiPicture *in, MiPicture *src);
 // The source half of DisplayArgs: planes, strides, vector-load flags, sizes, siting, H and M.
 void display_source(const MiPicture &src, const MiColorInfo *color, DisplayArgs &a);
 
+// ---- host (tonemap.cpp) ----
+// The rules of the colour-volume stage for `tm` and the source description in `color` (not NULL):
+// 0, -EINVAL or -ENOTSUP as include/mi_av1out.h lists them. No device work.
+int tone_check(const MiToneMap *tm, const MiColorInfo *color);
+// The context's device tables for (tm, color, src_bpc), all checked before: built and uploaded on
+// `s` when they differ from the ones it holds. 0, -ENOMEM or -EIO (with last_error set).
+int tone_prepare(MiCtx *ctx, const MiToneMap *tm, const MiColorInfo *color, int src_bpc, hipStream_t s, ToneArgs &t);
+
 // ---- device ----
+
+// The stage reads lut_in from the workgroup's copy in LDS and lut_out (128 KB) from global memory.
+// lut_in was measured both ways (the colour-volume stage): from LDS the calls take
+// 0.74 - 0.80 of the time they take with lut_in in global memory at 10 bits, 0.69 - 0.74 at 12.
+constexpr int kToneIn = 4096;   // entries of lut_in at 12 bits
+
+// the workgroup's copy of lut_in: every thread calls it, a barrier follows
+__device__ __forceinline__ void tone_stage(const ToneArgs &tm, float *lds, int tid, int nthreads) {
+    for (int i = 4 * tid; i < tm.n_in; i += 4 * nthreads)
+        *reinterpret_cast<float4 *>(lds + i) = *reinterpret_cast<const float4 *>(tm.lut_in + i);
+}
+
+// 8 pixels of source-coded R'G'B' to destination-coded R'G'B', in place; `lin` is the workgroup's
+// copy of lut_in. Every float32 operation is rounded on its own: the pragma keeps the compiler from
+// contracting the products and sums into fused multiply-adds (as scale_bias in tensor.hip).
+__device__ __forceinline__ void tone_run(const ToneArgs &tm, const float *lin, int (&R)[8], int (&G)[8], int (&B)[8]) {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        // (the matrix clips to [0, Ms]; the identity hands samples on, which a valid picture
+        // keeps in that range: the min holds the index inside the table whatever the planes hold)
+        const int top = tm.n_in - 1;
+        const float r = lin[min(R[k], top)], g = lin[min(G[k], top)], b = lin[min(B[k], top)];
+        int o[3];
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            const float p0 = tm.m[3 * c] * r, p1 = tm.m[3 * c + 1] * g, p2 = tm.m[3 * c + 2] * b;
+            const float s = p0 + p1;
+            const float t = fminf(fmaxf(s + p2, 0.0f), 1.0f);
+            const float q = t * 65535.0f;
+            o[c] = (int)tm.lut_out[(int)(q + 0.5f)];
+        }
+        R[k] = o[0];
+        G[k] = o[1];
+        B[k] = o[2];
+    }
+}
 
 // N samples of a plane row from column x0, columns clamped to pw - 1
 template <typename Px, int N>

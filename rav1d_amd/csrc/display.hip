@@ -12,6 +12,11 @@
 // are 16-byte aligned and the run lies inside the row; any other run is done sample by sample
 // with clamped source columns. Packed RGBA, whose runs are 2 or 4 vectors long, goes through a
 // per-wave LDS hand-off so that a store instruction writes 1 KB contiguously (rgb_row).
+//
+// mi_display_picture_tm is the same kernel with the colour-volume stage (display.h tone_run: two
+// table gathers per channel around a 3 x 3 float32 matrix) between the matrix and the store, a
+// compile-time switch; its destination samples have the type of dst_bpc, not the source's. The
+// instantiations without the stage are the code they were before it existed.
 #include <cerrno>
 #include <cmath>
 #include <cstring>
@@ -51,12 +56,18 @@ __device__ __forceinline__ void store_run(uint8_t *row, int s0, int limit, bool 
     }
 }
 
-// 8 pixels of luma row `row` to R'G'B'
-template <typename Px, int FMT>
-__device__ __forceinline__ void rgb_row(const DisplayArgs &a, int row, int x0, const int (&y)[8], const int (&cu)[8],
-                                        const int (&cv)[8]) {
+// 8 pixels of luma row `row` to R'G'B' samples of type Px (the destination's: the source's own
+// type, or with the colour-volume stage TM the type of dst_bpc)
+template <typename Px, int FMT, bool TM>
+__device__ __forceinline__ void rgb_row(const DisplayArgs &a, const ToneParam<TM> &tm, const float *lin, int row, int x0,
+                                        const int (&y)[8], const int (&cu)[8], const int (&cv)[8]) {
     int R[8], G[8], B[8];
     convert_run(a, y, cu, cv, R, G, B);
+    int alpha = a.maxv;
+    if constexpr (TM) {
+        tone_run(tm, lin, R, G, B);
+        alpha = tm.maxd;
+    }
     if constexpr (FMT == MI_OUT_RGB_PLANAR) {
         store_run<Px, 8>(a.dst[0] + row * a.dstride[0], x0, a.w, a.dvec & 1, R);
         store_run<Px, 8>(a.dst[1] + row * a.dstride[1], x0, a.w, (a.dvec >> 1) & 1, G);
@@ -68,7 +79,7 @@ __device__ __forceinline__ void rgb_row(const DisplayArgs &a, int row, int x0, c
             o[4 * k] = R[k];
             o[4 * k + 1] = G[k];
             o[4 * k + 2] = B[k];
-            o[4 * k + 3] = a.maxv;
+            o[4 * k + 3] = alpha;
         }
         uint8_t *drow = a.dst[0] + row * a.dstride[0];
         // A lane's run is 32 samples (2 or 4 16-B vectors), so lane-owned stores would put each
@@ -110,8 +121,17 @@ __device__ __forceinline__ void rgb_row(const DisplayArgs &a, int row, int x0, c
     }
 }
 
-template <typename Px, int FMT>
-__global__ __launch_bounds__(256) void display_kernel(const DisplayArgs a) {
+// Px: the source samples; Dx: the destination samples (Px unless TM); TM: the colour-volume
+// stage after the matrix (RGB formats)
+template <typename Px, typename Dx, int FMT, bool TM>
+__global__ __launch_bounds__(256) void display_kernel(const DisplayArgs a, const ToneParam<TM> tm) {
+    [[maybe_unused]] const float *lin = nullptr;
+    if constexpr (TM) {   // (before any lane leaves: every lane fills the table and meets the barrier)
+        __shared__ __attribute__((aligned(16))) float lut[kToneIn];
+        tone_stage(tm, lut, threadIdx.y * 64 + threadIdx.x, 256);
+        __syncthreads();
+        lin = lut;
+    }
     const int cx = blockIdx.x * 64 + threadIdx.x, u = blockIdx.y * 4 + threadIdx.y;
     if (cx >= a.chunks || u >= a.units) return;
     const int x0 = cx * 8, nrows = 1 + a.ss_ver, r0 = u * nrows;
@@ -165,8 +185,8 @@ __global__ __launch_bounds__(256) void display_kernel(const DisplayArgs a) {
             upsample<Px>(a, 1, u, x0, cu);
             upsample<Px>(a, 2, u, x0, cv);
         }
-        rgb_row<Px, FMT>(a, r0, x0, y[0], cu[0], cv[0]);
-        if (a.ss_ver && r0 + 1 < a.h) rgb_row<Px, FMT>(a, r0 + 1, x0, y[1], cu[1], cv[1]);
+        rgb_row<Dx, FMT, TM>(a, tm, lin, r0, x0, y[0], cu[0], cv[0]);
+        if (a.ss_ver && r0 + 1 < a.h) rgb_row<Dx, FMT, TM>(a, tm, lin, r0 + 1, x0, y[1], cu[1], cv[1]);
     }
 }
 
@@ -174,10 +194,20 @@ template <typename Px>
 int launch_px(const DisplayArgs &a, int format, hipStream_t s) {
     const dim3 block(64, 4), grid((a.chunks + 63) / 64, (a.units + 3) / 4);
     switch (format) {
-    case MI_OUT_SEMIPLANAR: display_kernel<Px, MI_OUT_SEMIPLANAR><<<grid, block, 0, s>>>(a); break;
-    case MI_OUT_RGB_PLANAR: display_kernel<Px, MI_OUT_RGB_PLANAR><<<grid, block, 0, s>>>(a); break;
-    default: display_kernel<Px, MI_OUT_RGBA_PACKED><<<grid, block, 0, s>>>(a); break;
+    case MI_OUT_SEMIPLANAR: display_kernel<Px, Px, MI_OUT_SEMIPLANAR, false><<<grid, block, 0, s>>>(a, NoTone()); break;
+    case MI_OUT_RGB_PLANAR: display_kernel<Px, Px, MI_OUT_RGB_PLANAR, false><<<grid, block, 0, s>>>(a, NoTone()); break;
+    default: display_kernel<Px, Px, MI_OUT_RGBA_PACKED, false><<<grid, block, 0, s>>>(a, NoTone()); break;
     }
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+template <typename Px, typename Dx>
+int launch_tm(const DisplayArgs &a, const ToneArgs &tm, int format, hipStream_t s) {
+    const dim3 block(64, 4), grid((a.chunks + 63) / 64, (a.units + 3) / 4);
+    if (format == MI_OUT_RGB_PLANAR)
+        display_kernel<Px, Dx, MI_OUT_RGB_PLANAR, true><<<grid, block, 0, s>>>(a, tm);
+    else
+        display_kernel<Px, Dx, MI_OUT_RGBA_PACKED, true><<<grid, block, 0, s>>>(a, tm);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -185,6 +215,12 @@ int launch_px(const DisplayArgs &a, int format, hipStream_t s) {
 
 int launch_display(const DisplayArgs &a, int bpc, int format, hipStream_t s) {
     return bpc == 8 ? launch_px<uint8_t>(a, format, s) : launch_px<uint16_t>(a, format, s);
+}
+
+int launch_display_tm(const DisplayArgs &a, const ToneArgs &tm, int bpc, int dst_bpc, int format, hipStream_t s) {
+    if (bpc == 8)
+        return dst_bpc == 8 ? launch_tm<uint8_t, uint8_t>(a, tm, format, s) : launch_tm<uint8_t, uint16_t>(a, tm, format, s);
+    return dst_bpc == 8 ? launch_tm<uint16_t, uint8_t>(a, tm, format, s) : launch_tm<uint16_t, uint16_t>(a, tm, format, s);
 }
 
 
@@ -273,24 +309,31 @@ void display_source(const MiPicture &src, const MiColorInfo *color, DisplayArgs 
 
 }  // namespace mi
 
-extern "C" int mi_display_picture(MiCtx *ctx, const MiPicture *in, const MiDisplayImage *out, const MiColorInfo *color,
-                                  const MiFilmGrainData *fg, void *stream) {
+namespace {
+
+// mi_display_picture (tone false; tm not read) and mi_display_picture_tm (tone true)
+int display_picture(MiCtx *ctx, const MiPicture *in, const MiDisplayImage *out, const MiColorInfo *color, bool tone,
+                    const MiToneMap *tm, const MiFilmGrainData *fg, void *stream) {
     if (!in || !out || !in->data[0] || in->w <= 0 || in->h <= 0 || in->w > 65536 || in->h > 65536 ||
         in->layout < 0 || in->layout > 3 || (in->bpc != 8 && in->bpc != 10 && in->bpc != 12) || in->stride[0] <= 0)
         return -EINVAL;
     if (in->layout && (!in->data[1] || !in->data[2] || in->stride[1] <= 0)) return -EINVAL;
-    if (out->w != in->w || out->h != in->h || out->bpc != in->bpc) return -EINVAL;
+    if (out->w != in->w || out->h != in->h) return -EINVAL;
+    // the output depth: the source's, or with the colour-volume stage dst_bpc (checked below)
+    if (tone ? out->bpc != 8 && out->bpc != 10 && out->bpc != 12 : out->bpc != in->bpc) return -EINVAL;
     if (out->format != MI_OUT_SEMIPLANAR && out->format != MI_OUT_RGB_PLANAR && out->format != MI_OUT_RGBA_PACKED)
         return -EINVAL;
+    if (tone && out->format == MI_OUT_SEMIPLANAR) return -ENOTSUP;
     const int pxb = in->bpc == 8 ? 1 : 2, ss_hor = in->layout == 1 || in->layout == 2, ss_ver = in->layout == 1;
+    const int dpxb = out->bpc == 8 ? 1 : 2;   // bytes of a destination sample
     const int cw = (in->w + ss_hor) >> ss_hor, ch = (in->h + ss_ver) >> ss_ver;
     // destination planes and the samples a row of each holds
     const int ndst = out->format == MI_OUT_RGB_PLANAR ? 3 : out->format == MI_OUT_SEMIPLANAR && in->layout ? 2 : 1;
     for (int p = 0; p < ndst; p++) {
         const int64_t samples = out->format == MI_OUT_RGBA_PACKED ? 4 * (int64_t)in->w
                               : out->format == MI_OUT_SEMIPLANAR && p ? 2 * (int64_t)cw : in->w;
-        if (!out->data[p] || out->stride[p] < samples * pxb) return -EINVAL;
-        if (((uintptr_t)out->data[p] | (uintptr_t)out->stride[p]) & (uintptr_t)(pxb - 1)) return -EINVAL;
+        if (!out->data[p] || out->stride[p] < samples * dpxb) return -EINVAL;
+        if (((uintptr_t)out->data[p] | (uintptr_t)out->stride[p]) & (uintptr_t)(dpxb - 1)) return -EINVAL;
     }
     if ((int64_t)in->stride[0] < (int64_t)in->w * pxb || (in->layout && (int64_t)in->stride[1] < (int64_t)cw * pxb))
         return -EINVAL;
@@ -299,8 +342,16 @@ extern "C" int mi_display_picture(MiCtx *ctx, const MiPicture *in, const MiDispl
     memset(&a, 0, sizeof(a));
     if (out->format != MI_OUT_SEMIPLANAR)
         if (int e = mi::display_color(in, color, a)) return e;
+    if (tone) {
+        if (int e = mi::tone_check(tm, color)) return e;
+        if (out->bpc != tm->dst_bpc) return -EINVAL;
+    }
     if (!ctx) return -EINVAL;
 
+    // allocations and the table upload first: a call that fails there has launched nothing
+    mi::ToneArgs ta;
+    if (tone)
+        if (int e = mi::tone_prepare(ctx, tm, color, in->bpc, (hipStream_t)stream, ta)) return e;
     MiPicture src = *in;
     if (fg) {
         if (int e = mi::display_grain_picture(ctx, in, &src)) return e;
@@ -316,6 +367,20 @@ extern "C" int mi_display_picture(MiCtx *ctx, const MiPicture *in, const MiDispl
     a.shift = out->format == MI_OUT_SEMIPLANAR && in->bpc > 8 ? 16 - in->bpc : 0;
     a.chunks = (in->w + 7) >> 3;
     a.units = ss_ver ? ch : in->h;
-    if (mi::launch_display(a, in->bpc, out->format, (hipStream_t)stream)) return ctx->last_error = -EIO;
+    if (tone ? mi::launch_display_tm(a, ta, in->bpc, out->bpc, out->format, (hipStream_t)stream)
+             : mi::launch_display(a, in->bpc, out->format, (hipStream_t)stream))
+        return ctx->last_error = -EIO;
     return 0;
+}
+
+}  // namespace
+
+extern "C" int mi_display_picture(MiCtx *ctx, const MiPicture *in, const MiDisplayImage *out, const MiColorInfo *color,
+                                  const MiFilmGrainData *fg, void *stream) {
+    return display_picture(ctx, in, out, color, false, nullptr, fg, stream);
+}
+
+extern "C" int mi_display_picture_tm(MiCtx *ctx, const MiPicture *in, const MiDisplayImage *out, const MiColorInfo *color,
+                                     const MiToneMap *tm, const MiFilmGrainData *fg, void *stream) {
+    return display_picture(ctx, in, out, color, true, tm, fg, stream);
 }

@@ -22,6 +22,9 @@
 //                        destination's order, as whole vectors where the pointer and strides allow.
 // Both passes run every slot of the tap table (zero weights past an output's own taps): with one
 // trip count the loops unroll and the loads of several taps are in flight together.
+//
+// mi_display_tensor_tm: the colour-volume stage (display.h tone_run) runs in the tile fill of
+// tensor_h_kernel, a compile-time switch, so the passes resize the tone-mapped picture at dst_bpc.
 #include <algorithm>
 #include <cerrno>
 #include <cmath>
@@ -82,11 +85,14 @@ __global__ __launch_bounds__(256) void tensor_taps_kernel(const TensorArgs t) {
         axis_taps(t.ch, t.oh, i - t.ow, t.tv, vs, vs + t.oh, vs + 2 * t.oh);
 }
 
-// 8 pixels of one row to R'G'B', one 16-byte LDS write per channel at column `col` of the tile
-__device__ __forceinline__ void tile_row(const DisplayArgs &a, const int (&y)[8], const int (&cu)[8], const int (&cv)[8],
-                                         uint16_t (&tile)[3][kTensorSeg], int col) {
+// 8 pixels of one row to R'G'B' (with TM: through the colour-volume stage, to samples of dst_bpc),
+// one 16-byte LDS write per channel at column `col` of the tile
+template <bool TM>
+__device__ __forceinline__ void tile_row(const DisplayArgs &a, const ToneParam<TM> &tm, const float *lin, const int (&y)[8],
+                                         const int (&cu)[8], const int (&cv)[8], uint16_t (&tile)[3][kTensorSeg], int col) {
     int R[8], G[8], B[8];
     convert_run(a, y, cu, cv, R, G, B);
+    if constexpr (TM) tone_run(tm, lin, R, G, B);
     *reinterpret_cast<uint4 *>(&tile[0][col]) = make_uint4((uint32_t)R[0] | ((uint32_t)R[1] << 16), (uint32_t)R[2] | ((uint32_t)R[3] << 16),
                                                            (uint32_t)R[4] | ((uint32_t)R[5] << 16), (uint32_t)R[6] | ((uint32_t)R[7] << 16));
     *reinterpret_cast<uint4 *>(&tile[1][col]) = make_uint4((uint32_t)G[0] | ((uint32_t)G[1] << 16), (uint32_t)G[2] | ((uint32_t)G[3] << 16),
@@ -96,9 +102,16 @@ __device__ __forceinline__ void tile_row(const DisplayArgs &a, const int (&y)[8]
 }
 
 // ---- horizontal pass ----
-template <typename Px>
-__global__ __launch_bounds__(256) void tensor_h_kernel(const TensorArgs t) {
+template <typename Px, bool TM>
+__global__ __launch_bounds__(256) void tensor_h_kernel(const TensorArgs t, const ToneParam<TM> tm) {
     __shared__ __attribute__((aligned(16))) uint16_t tile[2][3][kTensorSeg];
+    [[maybe_unused]] const float *lin = nullptr;
+    if constexpr (TM) {
+        __shared__ __attribute__((aligned(16))) float lut[kToneIn];
+        tone_stage(tm, lut, threadIdx.x, 256);
+        __syncthreads();
+        lin = lut;
+    }
     const DisplayArgs &a = t.d;
     const int u = t.u0 + blockIdx.x, nrows = 1 + a.ss_ver, r0 = u * nrows;
     const int o0 = blockIdx.y * t.ob, o1 = min(o0 + t.ob, t.ow) - 1;
@@ -116,8 +129,8 @@ __global__ __launch_bounds__(256) void tensor_h_kernel(const TensorArgs t) {
             upsample<Px>(a, 1, u, x0, cu);
             upsample<Px>(a, 2, u, x0, cv);
         }
-        if (rows & 1) tile_row(a, y[0], cu[0], cv[0], tile[0], x0 - xa);
-        if (rows & 2) tile_row(a, y[1], cu[1], cv[1], tile[1], x0 - xa);
+        if (rows & 1) tile_row<TM>(a, tm, lin, y[0], cu[0], cv[0], tile[0], x0 - xa);
+        if (rows & 2) tile_row<TM>(a, tm, lin, y[1], cu[1], cv[1], tile[1], x0 - xa);
     }
     __syncthreads();
     // a lane owns (row, output column) items: per tap one weight (coalesced along o) and the
@@ -274,16 +287,22 @@ void launch_v(const TensorArgs &t, int order, dim3 grid, hipStream_t s) {
 
 }  // namespace
 
-int launch_tensor(const TensorArgs &t, int bpc, int order, bool taps, hipStream_t s) {
+int launch_tensor(const TensorArgs &t, int bpc, int order, bool taps, hipStream_t s, const ToneArgs *tm) {
     if (taps) {
         tensor_taps_kernel<<<(t.ow + t.oh + 255) / 256, 256, 0, s>>>(t);
         if (hipGetLastError() != hipSuccess) return -1;
     }
     const dim3 hgrid(t.units, t.segs);
-    if (bpc == 8)
-        tensor_h_kernel<uint8_t><<<hgrid, 256, 0, s>>>(t);
-    else
-        tensor_h_kernel<uint16_t><<<hgrid, 256, 0, s>>>(t);
+    if (tm) {
+        if (bpc == 8)
+            tensor_h_kernel<uint8_t, true><<<hgrid, 256, 0, s>>>(t, *tm);
+        else
+            tensor_h_kernel<uint16_t, true><<<hgrid, 256, 0, s>>>(t, *tm);
+    } else if (bpc == 8) {
+        tensor_h_kernel<uint8_t, false><<<hgrid, 256, 0, s>>>(t, NoTone());
+    } else {
+        tensor_h_kernel<uint16_t, false><<<hgrid, 256, 0, s>>>(t, NoTone());
+    }
     if (hipGetLastError() != hipSuccess) return -1;
     const dim3 vgrid((unsigned)t.xblocks * (unsigned)t.oh);
     switch (t.dtype) {
@@ -297,8 +316,11 @@ int launch_tensor(const TensorArgs &t, int bpc, int order, bool taps, hipStream_
 
 }  // namespace mi
 
-extern "C" int mi_display_tensor(MiCtx *ctx, const MiPicture *in, const MiTensorImage *out, const MiColorInfo *color,
-                                 const MiFilmGrainData *fg, void *stream) {
+namespace {
+
+// mi_display_tensor (tone false; tm not read) and mi_display_tensor_tm (tone true)
+int display_tensor(MiCtx *ctx, const MiPicture *in, const MiTensorImage *out, const MiColorInfo *color, bool tone,
+                   const MiToneMap *tm, const MiFilmGrainData *fg, void *stream) {
     if (!in || !out || !in->data[0] || in->w <= 0 || in->h <= 0 || in->w > 65536 || in->h > 65536 ||
         in->layout < 0 || in->layout > 3 || (in->bpc != 8 && in->bpc != 10 && in->bpc != 12) || in->stride[0] <= 0)
         return -EINVAL;
@@ -329,6 +351,8 @@ extern "C" int mi_display_tensor(MiCtx *ctx, const MiPicture *in, const MiTensor
     mi::TensorArgs t;
     memset(&t, 0, sizeof(t));
     if (int e = mi::display_color(in, color, t.d)) return e;
+    if (tone)
+        if (int e = mi::tone_check(tm, color)) return e;
     if (!ctx) return -EINVAL;
 
     // geometry of the passes and of the scratch
@@ -362,6 +386,9 @@ extern "C" int mi_display_tensor(MiCtx *ctx, const MiPicture *in, const MiTensor
     // reuses them, ordered behind their launch on the context's stream.
     const int geom[4] = {cw, ow, ch, oh};
     const bool taps = memcmp(geom, ctx->tens_geom, sizeof(geom)) != 0;
+    mi::ToneArgs ta;
+    if (tone)
+        if (int e = mi::tone_prepare(ctx, tm, color, in->bpc, (hipStream_t)stream, ta)) return e;
     MiPicture src = *in;
     if (fg) {
         if (int e = mi::display_grain_picture(ctx, in, &src)) return e;
@@ -374,7 +401,7 @@ extern "C" int mi_display_tensor(MiCtx *ctx, const MiPicture *in, const MiTensor
     t.dst = (uint8_t *)out->data;
     for (int i = 0; i < 3; i++) t.dstride[i] = out->stride[i];
     t.dtype = out->dtype;
-    t.shift = in->bpc - 8;
+    t.shift = (tone ? tm->dst_bpc : in->bpc) - 8;   // the picture the passes resize has this depth
     for (int c = 0; c < 3; c++) t.scale[c] = out->scale[c], t.bias[c] = out->bias[c];
     // the two fast orders, and whether every run of 4 elements is an aligned vector
     int order = mi::kTensorAny;
@@ -387,7 +414,19 @@ extern "C" int mi_display_tensor(MiCtx *ctx, const MiPicture *in, const MiTensor
         t.vec = !(((uintptr_t)out->data | (uintptr_t)out->stride[1]) & v4);
     }
     memset(ctx->tens_geom, 0, sizeof(ctx->tens_geom));
-    if (mi::launch_tensor(t, in->bpc, order, taps, (hipStream_t)stream)) return ctx->last_error = -EIO;
+    if (mi::launch_tensor(t, in->bpc, order, taps, (hipStream_t)stream, tone ? &ta : nullptr)) return ctx->last_error = -EIO;
     memcpy(ctx->tens_geom, geom, sizeof(geom));
     return 0;
+}
+
+}  // namespace
+
+extern "C" int mi_display_tensor(MiCtx *ctx, const MiPicture *in, const MiTensorImage *out, const MiColorInfo *color,
+                                 const MiFilmGrainData *fg, void *stream) {
+    return display_tensor(ctx, in, out, color, false, nullptr, fg, stream);
+}
+
+extern "C" int mi_display_tensor_tm(MiCtx *ctx, const MiPicture *in, const MiTensorImage *out, const MiColorInfo *color,
+                                    const MiToneMap *tm, const MiFilmGrainData *fg, void *stream) {
+    return display_tensor(ctx, in, out, color, true, tm, fg, stream);
 }

@@ -2,9 +2,12 @@
 torch tensor on the device, semi-planar YUV (NV12 / P010 and their 4:2:2 / 4:4:4 kin) or R'G'B'
 (planar, or packed with alpha), with film grain applied. torch allocates; the conversion is the
 gfx950 kernel of csrc/display.hip. display_tensor (mi_display_tensor, csrc/tensor.hip) writes the
-cropped, resized, normalised R'G'B' tensor an ML consumer reads."""
+cropped, resized, normalised R'G'B' tensor an ML consumer reads. With a ToneMap both go through the
+colour-volume stage (mi_display_picture_tm / mi_display_tensor_tm: inverse transfer and, for PQ, the
+BT.2390 tone curve, primaries conversion, the destination's OETF at a chosen depth) in the same pass."""
 import ctypes
 
+import numpy as np
 import torch
 
 from . import MiFilmGrainData, MiPicture, check, lib
@@ -28,9 +31,12 @@ class DisplayImage:
     (view them as uint16 on the host: numpy()). format "nv12" (or 0): `y` (h, w) and `uv`
     (ch, cw, 2) at the layout's own subsampling (None for 4:0:0), 10 / 12-bit samples MSB-aligned;
     "rgb" (1): `rgb` (3, h, w); "rgba" (2): `rgba` (h, w, 4), alpha 2^bpc - 1; RGB samples are
-    full range at the source bit depth, LSB-aligned."""
+    full range at the source bit depth, LSB-aligned. out_bpc: the depth of the samples when it
+    differs from the picture's (a tone-mapped RGB destination: ToneMap.dst_bpc); `bpc` is then
+    that depth."""
 
-    def __init__(self, w, h, bpc, layout, format, device="cuda"):
+    def __init__(self, w, h, bpc, layout, format, device="cuda", out_bpc=None):
+        bpc = bpc if out_bpc is None else int(out_bpc)
         self.w, self.h, self.bpc, self.layout = w, h, bpc, layout
         self.format = FORMATS[format] if isinstance(format, str) else int(format)
         if self.format not in FORMATS.values():
@@ -76,19 +82,52 @@ class DisplayImage:
         return out
 
 
-def display_picture(ctx, frame, image, color=None, fg=None, stream=None):
+class MiToneMap(ctypes.Structure):
+    _fields_ = [("dst_pri", ctypes.c_int32), ("dst_trc", ctypes.c_int32), ("dst_bpc", ctypes.c_int32),
+                ("src_peak", ctypes.c_float), ("dst_peak", ctypes.c_float)]
+
+
+def ToneMap(dst_pri=1, dst_trc=13, dst_bpc=8, src_peak=1000.0, dst_peak=100.0):
+    """A MiToneMap: the output's primaries (1 BT.709, 9 BT.2020, 12 P3-D65), OETF (1 BT.709,
+    13 sRGB) and depth (8, 10, 12), and for PQ sources the mastering and the target peak in nits.
+    The defaults take HDR10 to 8-bit sRGB at 100 nits."""
+    return MiToneMap(int(dst_pri), int(dst_trc), int(dst_bpc), float(src_peak), float(dst_peak))
+
+
+def tonemap_tables(tm, color, src_bpc):
+    """mi_tonemap_tables (host only): (lut_in float32 [1 << src_bpc], m float32 [3, 3],
+    lut_out uint16 [65536]), the tables the device stage uses for a source of `src_bpc` bits
+    described by color.pri and color.trc. Raises MiError on a negative return."""
+    lut_in = np.empty(1 << src_bpc if src_bpc in (8, 10, 12) else 1, dtype=np.float32)
+    m = np.empty(9, dtype=np.float32)
+    lut_out = np.empty(65536, dtype=np.uint16)
+    check(lib().mi_tonemap_tables(ctypes.byref(tm) if tm is not None else None,
+                                  ctypes.byref(color) if color is not None else None, int(src_bpc),
+                                  lut_in.ctypes.data_as(ctypes.c_void_p), m.ctypes.data_as(ctypes.c_void_p),
+                                  lut_out.ctypes.data_as(ctypes.c_void_p)), "mi_tonemap_tables")
+    return lut_in, m.reshape(3, 3), lut_out
+
+
+def display_picture(ctx, frame, image, color=None, fg=None, stream=None, tonemap=None):
     """Enqueue mi_display_picture: `frame` (a device Frame or a MiPicture) into `image` (a
     DisplayImage or a MiDisplayImage), with film grain when `fg` (a MiFilmGrainData or a
     make_fg_params dict). color: a MiColorInfo, needed by the RGB formats (its mtrx picks the
-    matrix, range the scaling, chr the 4:2:0 chroma siting). Raises MiError on a negative return."""
+    matrix, range the scaling, chr the 4:2:0 chroma siting). tonemap: a MiToneMap (ToneMap()):
+    the call is mi_display_picture_tm, color.pri and color.trc describe the source, and `image`
+    holds samples of tonemap.dst_bpc bits (DisplayImage(..., out_bpc=)). Raises MiError on a
+    negative return."""
     from .frame import _stream_ptr, film_grain_data
     src = frame if isinstance(frame, MiPicture) else frame.picture()
     im = image if isinstance(image, MiDisplayImage) else image.image()
     if fg is not None and not isinstance(fg, MiFilmGrainData):
         fg = film_grain_data(fg)
-    check(lib().mi_display_picture(ctx.h, ctypes.byref(src), ctypes.byref(im),
-                                   ctypes.byref(color) if color is not None else None,
-                                   ctypes.byref(fg) if fg is not None else None, _stream_ptr(stream)),
+    cp = ctypes.byref(color) if color is not None else None
+    fp = ctypes.byref(fg) if fg is not None else None
+    if tonemap is not None:
+        check(lib().mi_display_picture_tm(ctx.h, ctypes.byref(src), ctypes.byref(im), cp, ctypes.byref(tonemap), fp,
+                                          _stream_ptr(stream)), "mi_display_picture_tm")
+        return
+    check(lib().mi_display_picture(ctx.h, ctypes.byref(src), ctypes.byref(im), cp, fp, _stream_ptr(stream)),
           "mi_display_picture")
 
 
@@ -132,25 +171,34 @@ def tensor_image(out, bpc, crop=None, mean=None, std=None, channels_last=False):
     return im
 
 
-def display_tensor(ctx, frame, out, color, fg=None, crop=None, mean=None, std=None, stream=None, channels_last=False):
+def display_tensor(ctx, frame, out, color, fg=None, crop=None, mean=None, std=None, stream=None, channels_last=False,
+                   tonemap=None):
     """Enqueue mi_display_tensor: `frame` (a device Frame or a MiPicture) cropped to `crop`
     ((x, y, w, h) in luma pixels; None: the whole picture), resized to the size of `out` and
     normalised, as R'G'B' into `out`: a device tensor of shape (3, H, W) in any strides (batch[n] of
     an NCHW or a channels-last batch), or (H, W, 3) with channels_last; dtype and strides are the
     tensor's. Float dtypes receive (v / M - mean[c]) / std[c] (defaults 0 and 1: [0, 1]), uint8
     the sample at 8 bits. color: a MiColorInfo, as for display_picture's RGB formats; fg: film
-    grain. `out` may also be a ready MiTensorImage. Raises MiError on a negative return."""
+    grain. `out` may also be a ready MiTensorImage. tonemap: a MiToneMap (ToneMap()): the call is
+    mi_display_tensor_tm, the resized picture is the tone-mapped one and M is 2^dst_bpc - 1. Raises
+    MiError on a negative return."""
     from .frame import _stream_ptr, film_grain_data
     src = frame if isinstance(frame, MiPicture) else frame.picture()
-    im = out if isinstance(out, MiTensorImage) else tensor_image(out, src.bpc, crop, mean, std, channels_last)
+    bpc = src.bpc if tonemap is None else tonemap.dst_bpc
+    im = out if isinstance(out, MiTensorImage) else tensor_image(out, bpc, crop, mean, std, channels_last)
     if fg is not None and not isinstance(fg, MiFilmGrainData):
         fg = film_grain_data(fg)
-    check(lib().mi_display_tensor(ctx.h, ctypes.byref(src), ctypes.byref(im),
-                                  ctypes.byref(color) if color is not None else None,
-                                  ctypes.byref(fg) if fg is not None else None, _stream_ptr(stream)),
+    cp = ctypes.byref(color) if color is not None else None
+    fp = ctypes.byref(fg) if fg is not None else None
+    if tonemap is not None:
+        check(lib().mi_display_tensor_tm(ctx.h, ctypes.byref(src), ctypes.byref(im), cp, ctypes.byref(tonemap), fp,
+                                         _stream_ptr(stream)), "mi_display_tensor_tm")
+        return
+    check(lib().mi_display_tensor(ctx.h, ctypes.byref(src), ctypes.byref(im), cp, fp, _stream_ptr(stream)),
           "mi_display_tensor")
 
 
 __all__ = ["DisplayImage", "MiDisplayImage", "MiColorInfo", "display_picture", "FORMATS",
            "OUT_SEMIPLANAR", "OUT_RGB_PLANAR", "OUT_RGBA_PACKED",
-           "MiTensorImage", "tensor_image", "display_tensor", "T_U8", "T_F16", "T_BF16", "T_F32"]
+           "MiTensorImage", "tensor_image", "display_tensor", "T_U8", "T_F16", "T_BF16", "T_F32",
+           "MiToneMap", "ToneMap", "tonemap_tables"]

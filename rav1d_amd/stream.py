@@ -86,8 +86,21 @@ def decode_ivf(ctx, data, stream=None, sync_each=True, inloop_filters=14, thread
     frame_end(ctx, stream)
 
 
+def _source_colour(color, tonemap, primaries, transfer):
+    """Apply the primaries / transfer overrides to `color`; with a tone map the source must be
+    described: nothing is guessed."""
+    if primaries is not None:
+        color.pri = int(primaries)
+    if transfer is not None:
+        color.trc = int(transfer)
+    if tonemap is not None and (color.pri == 2 or color.trc == 2):
+        raise ValueError(f"tonemap needs the source's primaries and transfer: the stream has pri {color.pri}, "
+                         f"trc {color.trc} (2: unspecified); pass primaries= / transfer=")
+
+
 def decode_to_tensors(ctx, data, format="nv12", apply_grain=True, matrix=None, stream=None, inloop_filters=14,
-                      threads=1, operating_point=0, all_layers=True, decode_frame_type="all", frame_size_limit=0):
+                      threads=1, operating_point=0, all_layers=True, decode_frame_type="all", frame_size_limit=0,
+                      tonemap=None, primaries=None, transfer=None):
     """Decode a stream (IVF, Annex B or section 5) on the device and yield, per shown picture in
     output order, (DisplayImage, MiColorInfo): the picture as a tight device tensor in `format`
     ("nv12": semi-planar at the stream's own subsampling and bit depth; "rgb": planar R'G'B';
@@ -101,7 +114,14 @@ def decode_to_tensors(ctx, data, format="nv12", apply_grain=True, matrix=None, s
     overrides the stream's. With matrix=None the stream's own mtrx is used, and a stream that
     leaves it unspecified (mtrx 2) gets BT.709 (1) when w >= 1280 or h > 576 and BT.601 (6)
     otherwise, the usual rule for untagged video. The MiColorInfo yielded carries the matrix that
-    was used. The other settings are decode_ivf's."""
+    was used.
+
+    tonemap: a rav1d_amd.display.ToneMap(): the RGB formats go through mi_display_picture_tm and
+    the image holds samples of tonemap.dst_bpc bits in the tone map's primaries and transfer.
+    primaries, transfer: Dav1dColorPrimaries / Dav1dTransferCharacteristics values that override
+    the stream's (as matrix does; the MiColorInfo yielded carries them). With tonemap, a stream
+    that leaves either unspecified and has no override raises ValueError. The other settings are
+    decode_ivf's."""
     from .av1dec import MiColorInfo
     from .display import FORMATS, OUT_SEMIPLANAR, DisplayImage, display_picture
     fmt = FORMATS[format] if isinstance(format, str) else int(format)
@@ -121,8 +141,11 @@ def decode_to_tensors(ctx, data, format="nv12", apply_grain=True, matrix=None, s
                         color.mtrx = int(matrix)
                     elif color.mtrx == 2:
                         color.mtrx = 1 if (src.w >= 1280 or src.h > 576) else 6
-                image = DisplayImage(src.w, src.h, src.bpc, src.layout, fmt)
-                display_picture(ctx, src, image, color, ev.fg if (ev.fg_present and apply_grain) else None, stream)
+                _source_colour(color, tonemap, primaries, transfer)
+                image = DisplayImage(src.w, src.h, src.bpc, src.layout, fmt,
+                                     out_bpc=tonemap.dst_bpc if tonemap is not None else None)
+                display_picture(ctx, src, image, color, ev.fg if (ev.fg_present and apply_grain) else None, stream,
+                                tonemap)
                 yield image, color
             for i in range(ev.n_release):
                 pics.pop(ev.release[i], None)
@@ -151,7 +174,8 @@ def fit_crop(w, h, W, H, fit):
 
 def decode_to_batches(ctx, data, size, batch=8, dtype=None, channels_last=False, mean=None, std=None, fit="stretch",
                       every=1, apply_grain=True, matrix=None, stream=None, inloop_filters=14, threads=1,
-                      operating_point=0, all_layers=True, decode_frame_type="all", frame_size_limit=0):
+                      operating_point=0, all_layers=True, decode_frame_type="all", frame_size_limit=0,
+                      tonemap=None, primaries=None, transfer=None):
     """Decode a stream on the device and yield (tensor, [MiColorInfo, ...]) batches for an ML
     consumer: the tensor is (n, 3, H, W) with size = (W, H), n = batch except for a shorter last
     one, of `dtype` (torch.float16 by default; bfloat16, float32 or uint8), contiguous or, with
@@ -160,7 +184,8 @@ def decode_to_batches(ctx, data, size, batch=8, dtype=None, channels_last=False,
     .display_tensor) into its slot: cropped per `fit` (fit_crop; pictures of different sizes in a
     stream each get their own crop), resized, normalised with mean / std per channel, with film
     grain when the frame carries it and apply_grain is set. The list holds the colour description
-    used for each slot; matrix follows decode_to_tensors's rule. Each tensor is a fresh allocation
+    used for each slot; matrix, tonemap, primaries and transfer follow decode_to_tensors's rules
+    (with tonemap the slot is mi_display_tensor_tm's: the tone-mapped picture, resized). Each tensor is a fresh allocation
     the caller owns, filled by work enqueued on `stream` (synchronise it, or stay on it, before
     reading). The other settings are decode_ivf's."""
     import torch
@@ -196,11 +221,12 @@ def decode_to_batches(ctx, data, size, batch=8, dtype=None, channels_last=False,
                         color.mtrx = int(matrix)
                     elif color.mtrx == 2:
                         color.mtrx = 1 if (src.w >= 1280 or src.h > 576) else 6
+                    _source_colour(color, tonemap, primaries, transfer)
                     if state["tensor"] is None:
                         new_batch()
                     display_tensor(ctx, src, state["tensor"][len(state["colors"])], color,
                                    ev.fg if (ev.fg_present and apply_grain) else None,
-                                   fit_crop(src.w, src.h, W, H, fit), mean, std, stream)
+                                   fit_crop(src.w, src.h, W, H, fit), mean, std, stream, tonemap=tonemap)
                     state["colors"].append(color)
                     if len(state["colors"]) == batch:
                         out = state["tensor"], state["colors"]

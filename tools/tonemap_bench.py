@@ -1,0 +1,138 @@
+#!/usr/bin/env python3
+"""Measure the colour-volume stage (mi_display_picture_tm, mi_display_tensor_tm) on a resident 4K10
+4:2:0 picture (GPU), each tone-mapped path beside the plain path it extends, timed in the same run
+with HIP events around `--iters` back-to-back calls after `--warmup` calls, the plain path on both
+sides of the tone-mapped one:
+
+  rgba10           mi_display_picture, packed RGBA at 10 bits (no stage);
+  rgba8_tm         mi_display_picture_tm, PQ / BT.2020 -> sRGB / BT.709, packed RGBA at 8 bits;
+  rgba10_tm        the same to 10 bits: the bytes of rgba10, so the difference is the stage alone;
+  tensor           mi_display_tensor to float16 CHW at --size;
+  tensor_tm        mi_display_tensor_tm, the same tone map at 8 bits, to the same tensor.
+
+The planes hold uniformly random codes, so the table gathers have no locality beyond the tables'
+size: decoded pictures are smoother. No threshold is asserted; the ratios are recorded.
+
+    python tools/tonemap_bench.py [--out profiles/tonemap_bench.json] [--note TEXT]
+
+A variant build of the library (MI_BUILD_VARIANT of rav1d_amd/build.py, loaded with MI_LIB) is
+measured by the same command with another --out; --note says which it was.
+"""
+import argparse
+import ctypes
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "tonemap_bench.json"))
+    ap.add_argument("--width", type=int, default=3840)
+    ap.add_argument("--height", type=int, default=2160)
+    ap.add_argument("--bpc", type=int, default=10)
+    ap.add_argument("--size", type=int, nargs=2, default=(224, 224), metavar=("W", "H"))
+    ap.add_argument("--iters", type=int, default=200)
+    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--note", default="")
+    args = ap.parse_args()
+
+    import numpy as np
+    import torch
+
+    from rav1d_amd import LIB_PATH, lib
+    from rav1d_amd.av1dec import MiColorInfo
+    from rav1d_amd.display import DisplayImage, ToneMap, tensor_image
+    from rav1d_amd.frame import Context, Frame
+
+    if not torch.cuda.is_available():
+        sys.exit("tonemap_bench needs a GPU: nothing is measured without one")
+    L = lib()
+    w, h, bpc, layout = args.width, args.height, args.bpc, 1
+    ow, oh = args.size
+    rng = np.random.default_rng(0)
+    ctx = Context(0)
+    src = Frame(w, h, bpc, layout)
+    for p in range(3):
+        pw, ph = src.dims(p)
+        src.set_plane_np(p, rng.integers(0, 1 << bpc, (ph, pw)))
+    color = MiColorInfo(9, 16, 9, 0, 0)      # HDR10: BT.2020 primaries and matrix, PQ, limited range
+    tm8, tm10 = ToneMap(1, 13, 8, 1000.0, 100.0), ToneMap(1, 13, 10, 1000.0, 100.0)
+    stream = torch.cuda.current_stream()
+    sp = ctypes.c_void_p(stream.cuda_stream)
+    pic = src.picture()
+    mean, std = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
+
+    im10, im8 = DisplayImage(w, h, bpc, layout, "rgba"), DisplayImage(w, h, bpc, layout, "rgba", out_bpc=8)
+    im10t = DisplayImage(w, h, bpc, layout, "rgba", out_bpc=10)
+    d10, d8, d10t = im10.image(), im8.image(), im10t.image()
+    out = torch.empty((3, oh, ow), dtype=torch.float16, device="cuda")
+    out_t = torch.empty((3, oh, ow), dtype=torch.float16, device="cuda")
+    t_plain, t_tm = tensor_image(out, bpc, None, mean, std), tensor_image(out_t, 8, None, mean, std)
+    # the C entries directly, on prebuilt arguments: the host side of a call stays well below the
+    # device time, so the events time the device
+    ref = ctypes.byref
+
+    def entry(fn, *argv):
+        def run():
+            if fn(*argv) != 0:
+                raise RuntimeError(f"{fn.__name__} failed")
+        return run
+
+    cases = {
+        "rgba10": entry(L.mi_display_picture, ctx.h, ref(pic), ref(d10), ref(color), None, sp),
+        "rgba8_tm": entry(L.mi_display_picture_tm, ctx.h, ref(pic), ref(d8), ref(color), ref(tm8), None, sp),
+        "rgba10_tm": entry(L.mi_display_picture_tm, ctx.h, ref(pic), ref(d10t), ref(color), ref(tm10), None, sp),
+        "tensor": entry(L.mi_display_tensor, ctx.h, ref(pic), ref(t_plain), ref(color), None, sp),
+        "tensor_tm": entry(L.mi_display_tensor_tm, ctx.h, ref(pic), ref(t_tm), ref(color), ref(tm8), None, sp),
+    }
+
+    def timed(fn):
+        """Median over rounds of the mean microseconds of `iters` back-to-back calls."""
+        for _ in range(args.warmup):
+            fn()
+        torch.cuda.synchronize()
+        us = []
+        for _ in range(args.rounds):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record(stream)
+            for _ in range(args.iters):
+                fn()
+            b.record(stream)
+            b.synchronize()
+            us.append(a.elapsed_time(b) * 1e3 / args.iters)
+        return float(np.median(us)), [round(v, 2) for v in us]
+
+    results = {}
+    order = ["rgba10", "rgba8_tm", "rgba10_tm", "rgba10", "tensor", "tensor_tm", "tensor"]
+    for name in order:
+        us, rounds = timed(cases[name])
+        key = name if name not in results else name + "_again"
+        results[key] = dict(us=round(us, 2), rounds_us=rounds)
+        print(json.dumps({key: results[key]}), flush=True)
+    plain = (results["rgba10"]["us"] + results["rgba10_again"]["us"]) / 2
+    tplain = (results["tensor"]["us"] + results["tensor_again"]["us"]) / 2
+    doc = dict(tool="tools/tonemap_bench.py", device=torch.cuda.get_device_name(0), library=os.path.basename(LIB_PATH),
+               note=args.note, width=w, height=h, bpc=bpc, layout="4:2:0", out_w=ow, out_h=oh,
+               source="PQ / BT.2020 (pri 9, trc 16, mtrx 9, limited), uniformly random codes",
+               tonemap="to sRGB / BT.709, src_peak 1000, dst_peak 100", iters=args.iters, warmup=args.warmup,
+               rounds=args.rounds, timing="HIP events around back-to-back calls; median of rounds", results=results,
+               rgba10_us=round(plain, 2), tensor_us=round(tplain, 2),
+               ratio_rgba8_tm_to_rgba10=round(results["rgba8_tm"]["us"] / plain, 3),
+               ratio_rgba10_tm_to_rgba10=round(results["rgba10_tm"]["us"] / plain, 3),
+               ratio_tensor_tm_to_tensor=round(results["tensor_tm"]["us"] / tplain, 3))
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(doc, f, indent=1)
+        f.write("\n")
+    print(json.dumps({k: doc[k] for k in ("rgba10_us", "tensor_us", "ratio_rgba8_tm_to_rgba10", "ratio_rgba10_tm_to_rgba10",
+                                          "ratio_tensor_tm_to_tensor")}))
+    print("wrote", args.out)
+
+
+if __name__ == "__main__":
+    main()
