@@ -4,7 +4,8 @@
  *
  * Two libraries implement it:
  *   - librav1d_amd.so (gfx950): mi_host_picture_alloc / _free, mi_output_picture, and the
- *     output that stays on the device, mi_display_picture and mi_display_tensor;
+ *     output that stays on the device, mi_display_picture, mi_display_tensor and
+ *     mi_display_scaled;
  *   - libmi_av1dec.so (host C++): the muxers mi_muxer_* (no GPU code).
  *
  * Reference: the CLI's output stage (tools/output/output.rs), its muxers md5
@@ -242,6 +243,62 @@ int mi_display_picture_tm(MiCtx *ctx, const MiPicture *in, const MiDisplayImage 
 int mi_display_tensor_tm(MiCtx *ctx, const MiPicture *in, const MiTensorImage *out,
                          const MiColorInfo *color, const MiToneMap *tm,
                          const MiFilmGrainData *fg, void *stream);
+
+/* ---- scaled semi-planar output (librav1d_amd.so) ------------------------------------------ */
+
+/* A shown picture as cropped, resized semi-planar YUV at a chosen depth, for an encoder on the
+ * device (a transcode ladder: one call writes up to 8 rungs). The output keeps the source's chroma
+ * subsampling and the storage of MI_OUT_SEMIPLANAR: data[0] = Y, data[1] = interleaved UV (NV12 /
+ * NV16 / NV24; 4:0:0 writes Y only and does not read data[1]), u8 at 8 bpc, else u16 MSB-aligned
+ * (v << (16 - bpc)). Only the w x h luma samples and the cw x ch UV pairs are written.
+ *
+ * sh, sv = the layout's subsampling shifts. The luma crop is crop_w x crop_h at (crop_x, crop_y),
+ * crop_w == 0 and crop_h == 0 the whole picture (crop_x, crop_y are not read then); the chroma crop
+ * is at (crop_x >> sh, crop_y >> sv) with extent ((crop_w + sh) >> sh, (crop_h + sv) >> sv), and the
+ * chroma output extent is cw x ch = ((w + sh) >> sh, (h + sv) >> sv). So that the two crops cover
+ * the same area, crop_x must be even with sh and crop_y with sv, and crop_w (crop_h) must be even
+ * with sh (sv) unless the crop reaches the picture's right (bottom) edge.
+ *
+ * resize: every plane on its own, separable, the horizontal pass first, its result an integer in
+ *   [0, Ms] (Ms = 2^in->bpc - 1) the vertical pass runs over; n_in the plane's crop extent, n_out
+ *   its output extent on the axis, S = 18.
+ *   Luma, and chroma on an axis that is not subsampled or whose samples are centred (every axis
+ *   of 4:4:4, the vertical axis of 4:2:2, the vertical axis of 4:2:0 with chr 0 or 1): the formula
+ *   of mi_display_tensor, Rr = 2 max(n_in, n_out), C = (2o+1) n_in, wt_i = Rr - |C - (2i+1) n_out|.
+ *   Chroma on a co-sited axis (the horizontal axis of 4:2:0 and 4:2:2, the vertical axis of 4:2:0
+ *   with chr == 2: the sitings the upsampler of the RGB formats assumes), where a chroma sample
+ *   sits on the even luma sample, a quarter of a chroma sample left of (above) its centre:
+ *   Rr = 4 max(n_in, n_out), C = (4o+1) n_in, wt_i = Rr - |C - (4i+1) n_out|.
+ *   Both: the taps are the i with wt_i > 0; W = sum wt_i, k_i = (wt_i 2^S + W/2) / W (floor);
+ *   2^S - sum k_i is added to the first tap with the largest wt_i; tap i reads crop sample
+ *   clamp(i, 0, n_in - 1); out[o] = (sum k_i x_i + 2^(S-1)) >> S. n_in == n_out is the identity
+ *   with either formula. A downscale above 64:1 on any plane axis (n_in > 64 n_out) is -EINVAL.
+ * depth: v the vertical pass's integer at the source depth s, d = bpc of the rung, Md = 2^d - 1:
+ *   d == s: v; d < s: min(Md, (v + 2^(s-d-1)) >> (s-d)); d > s: v << (d-s); then the store above.
+ * color may be NULL; only color->chr is read (NULL: 0), and it is the siting of the output too.
+ * With `fg`, film grain is applied once (mi_film_grain_frame, mtrx_identity = color &&
+ * color->mtrx == 0) into the context's scratch picture and every rung reads that. Each rung is
+ * defined from the (grained) source picture alone, never from another rung: a call with n_outs
+ * rungs equals n_outs calls with one rung, bit for bit. 1:1 at the source depth without a crop is
+ * MI_OUT_SEMIPLANAR of mi_display_picture. */
+typedef struct MiScaledImage {
+    void *data[2]; ptrdiff_t stride[2];   /* Y plane; interleaved UV plane (unused for 4:0:0) */
+    int32_t w, h;                         /* output luma size */
+    int32_t bpc;                          /* output depth 8, 10 or 12; need not equal in->bpc */
+    int32_t crop_x, crop_y, crop_w, crop_h;  /* luma pixels of `in`; crop_w == crop_h == 0: whole picture */
+} MiScaledImage;
+
+/* Enqueue the n_outs (1..8) scaled outputs of `in` on `stream` (never synchronises); the context
+ * owns the scratch (tap tables and the horizontal pass's result; allocated on first use, replaced
+ * only when a call needs more; a call with the geometry of the one before reuses the tables).
+ * Every check precedes any device work, the NULL `ctx` last: -EINVAL for NULL `in` / `outs`, a
+ * malformed `in`, n_outs outside 1..8; per rung a NULL data[0], a NULL data[1] with a chroma
+ * layout, w or h outside 1..65536, a bpc other than 8 / 10 / 12, a stride smaller than the row it
+ * holds or not a multiple of the sample size, a pointer not aligned to the sample size, a crop
+ * outside the picture or with one extent zero, an odd crop origin or extent as described above, a
+ * downscale above 64:1 on any plane axis; color->chr outside 0..2. -ENOMEM and -EIO as above. */
+int mi_display_scaled(MiCtx *ctx, const MiPicture *in, const MiScaledImage *outs, int n_outs,
+                      const MiColorInfo *color, const MiFilmGrainData *fg, void *stream);
 
 #ifdef __cplusplus
 }

@@ -230,6 +230,9 @@ def lib():
     _sig(L, "mi_tonemap_tables", ctypes.c_int, [_VP, _VP, ctypes.c_int, _VP, _VP, _VP])
     for n in ("mi_display_picture_tm", "mi_display_tensor_tm"):
         _sig(L, n, ctypes.c_int, [_VP, ctypes.POINTER(MiPicture), _VP, _VP, _VP, ctypes.POINTER(MiFilmGrainData), _VP])
+    # (MiScaledImage: rav1d_amd/display.py)
+    _sig(L, "mi_display_scaled", ctypes.c_int, [_VP, ctypes.POINTER(MiPicture), _VP, ctypes.c_int, _VP,
+                                                ctypes.POINTER(MiFilmGrainData), _VP])
     _lib = L
     return L
 
@@ -247,7 +250,8 @@ EXPORTED = ["mi_version", "mi_ctx_create", "mi_ctx_destroy", "mi_ctx_last_error"
             "mi_dsp_mc_scaled", "mi_dsp_lr_wiener", "mi_dsp_lr_sgr",
             "mi_dsp_fg_generate_grain_y", "mi_dsp_fg_generate_grain_uv", "mi_dsp_fgy_32x32xn", "mi_dsp_fguv_32x32xn",
             "mi_host_picture_alloc", "mi_host_picture_free", "mi_output_picture", "mi_display_picture",
-            "mi_display_tensor", "mi_tonemap_tables", "mi_display_picture_tm", "mi_display_tensor_tm"]
+            "mi_display_tensor", "mi_tonemap_tables", "mi_display_picture_tm", "mi_display_tensor_tm",
+            "mi_display_scaled"]
 
 
 def check(rc, what):

@@ -550,6 +550,39 @@ enum { kTensorCHW = 0, kTensorHWC = 1, kTensorAny = 2 };
 // tm: the colour-volume stage in the tile fill of the horizontal pass, or nullptr
 int launch_tensor(const TensorArgs &t, int bpc, int order, bool taps, hipStream_t s, const ToneArgs *tm = nullptr);
 
+// scaled semi-planar output (scaled.hip): per rung, the luma plane and the U / V pair each cropped,
+// resized (the separable 18-bit triangle filter of the tensor output, with the chroma siting in
+// the taps), converted to the rung's depth and stored as Y and interleaved UV.
+constexpr int kScaledSeg = 2048;  // source columns one workgroup of the horizontal pass holds
+struct ScaledPlane {              // luma (1 channel) or chroma (2 channels: U, V)
+    const uint8_t *src[2];
+    int64_t sstride;
+    int svec;                     // bit c: channel c's pointer and stride are 16-byte aligned
+    int pw;                       // plane width
+    int px, py, pcw, pch;         // the crop, samples of the plane
+    int ow, oh;                   // output extent
+    const int *htab, *vtab;       // per axis: start[n_out] count[n_out] k[cap][n_out]
+    int th, tv;                   // tap capacity per axis
+    uint16_t *mid;                // horizontal result: channel c at mid + c * pch * mstride
+    int64_t mstride;              // u16 per row of mid, a multiple of 8
+    int ob, segs;                 // horizontal pass: outputs per segment, segments
+    int xblocks;                  // vertical pass: workgroups per output row
+    uint8_t *dst;
+    int64_t dstride;
+    int dvec;                     // every lane's run of 4 samples (Y) or 4 pairs (UV) is an aligned vector
+};
+struct ScaledArgs {
+    ScaledPlane p[2];
+    int nplanes;                  // 1 for 4:0:0
+    int down;                     // depth: s - d when d < s, else 0
+    int up;                       // left shift after it: (d - s when d > s) + (16 - d when d > 8)
+    int maxd;                     // Md
+};
+struct ScaledAxis { int n_in, n_out, phase, cap; int *tab; };   // phase 2: centred, 4: co-sited
+struct ScaledTaps { ScaledAxis ax[32]; int n; };
+int launch_scaled_taps(const ScaledTaps &t, hipStream_t s);
+int launch_scaled(const ScaledArgs &a, int src_bpc, int dst_bpc, hipStream_t s);
+
 // ---- per-call (table-compatible) entry points: single-block kernels ----
 struct LfCallArgs {
     uint8_t *dst;

@@ -22,6 +22,12 @@ struct MiCtx {
     uint8_t *tens = nullptr;
     size_t tens_bytes = 0;
     int tens_geom[4] = {0, 0, 0, 0};   // crop w, out w, crop h, out h of the tap tables it holds (0: none)
+    // mi_display_scaled: its own tap tables and horizontal result (one allocation, replaced only
+    // when a call needs more); scal_key: the rung count and per rung the plane extents and tap
+    // phases of the tables it holds (all 0: none)
+    uint8_t *scal = nullptr;
+    size_t scal_bytes = 0;
+    int scal_key[1 + 8 * 10] = {0};
     // mi_display_*_tm: the device tables (lut_out, then lut_in) of the key `tone_key` (*tm with
     // the peaks zeroed for sources that do not read them, pri, trc, source bpc), their matrix, and
     // two pinned staging buffers used in turn; `tone_ev[i]` marks when buffer i may be rewritten
@@ -91,6 +97,7 @@ struct MiCtx {
         if (fg_offsets) (void)hipFree(fg_offsets);
         if (disp_fg) (void)hipFree(disp_fg);
         if (tens) (void)hipFree(tens);
+        if (scal) (void)hipFree(scal);
         if (tone_dev) (void)hipFree(tone_dev);
         for (int i = 0; i < 2; i++) {
             if (tone_ev[i]) (void)hipEventDestroy(tone_ev[i]);

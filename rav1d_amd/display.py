@@ -4,7 +4,9 @@ torch tensor on the device, semi-planar YUV (NV12 / P010 and their 4:2:2 / 4:4:4
 gfx950 kernel of csrc/display.hip. display_tensor (mi_display_tensor, csrc/tensor.hip) writes the
 cropped, resized, normalised R'G'B' tensor an ML consumer reads. With a ToneMap both go through the
 colour-volume stage (mi_display_picture_tm / mi_display_tensor_tm: inverse transfer and, for PQ, the
-BT.2390 tone curve, primaries conversion, the destination's OETF at a chosen depth) in the same pass."""
+BT.2390 tone curve, primaries conversion, the destination's OETF at a chosen depth) in the same pass.
+display_scaled (mi_display_scaled, csrc/scaled.hip) writes cropped, resized semi-planar YUV at a
+chosen depth, several sizes per call: the rungs of a transcode ladder."""
 import ctypes
 
 import numpy as np
@@ -198,7 +200,96 @@ def display_tensor(ctx, frame, out, color, fg=None, crop=None, mean=None, std=No
           "mi_display_tensor")
 
 
+class MiScaledImage(ctypes.Structure):
+    _fields_ = [("data", ctypes.c_void_p * 2), ("stride", ctypes.c_ssize_t * 2),
+                ("w", ctypes.c_int32), ("h", ctypes.c_int32), ("bpc", ctypes.c_int32),
+                ("crop_x", ctypes.c_int32), ("crop_y", ctypes.c_int32), ("crop_w", ctypes.c_int32),
+                ("crop_h", ctypes.c_int32)]
+
+
+def even_crop(crop, w, h, layout):
+    """`crop` ((x, y, cw, ch) in luma pixels of a w x h picture) moved onto the chroma grid of
+    `layout`, as mi_display_scaled asks: an odd origin on a subsampled axis goes one luma sample
+    left (up) and the extent grows by it, and an odd extent that does not reach the picture's edge
+    grows by one sample (it always fits: the edge it would pass is the odd one it may reach)."""
+    x, y, cw, ch = (int(v) for v in crop)
+    if layout in (1, 2):
+        cw, x = cw + (x & 1), x & ~1
+        if cw & 1 and x + cw != w:
+            cw += 1
+    if layout == 1:
+        ch, y = ch + (y & 1), y & ~1
+        if ch & 1 and y + ch != h:
+            ch += 1
+    return x, y, cw, ch
+
+
+class ScaledImage:
+    """One rung of display_scaled: a w x h semi-planar destination of `bpc` bits for a picture of
+    pixel `layout` (0 I400 .. 3 I444): `y` (h, w) and `uv` (ch, cw, 2) at the layout's own
+    subsampling (None for 4:0:0), uint8 at 8 bpc, else 16-bit words MSB-aligned held in int16
+    storage (view them as uint16 on the host: numpy()). crop: (x, y, w, h) in luma pixels of the
+    source, or None for the whole picture."""
+
+    def __init__(self, w, h, bpc, layout, crop=None, device="cuda"):
+        self.w, self.h, self.bpc, self.layout = int(w), int(h), int(bpc), layout
+        self.crop = None if crop is None else tuple(int(v) for v in crop)
+        dt = torch.uint8 if self.bpc == 8 else torch.int16
+        ss_hor, ss_ver = int(layout in (1, 2)), int(layout == 1)
+        self.cw, self.ch = (self.w + ss_hor) >> ss_hor, (self.h + ss_ver) >> ss_ver
+        self.y = torch.zeros((self.h, self.w), dtype=dt, device=device)
+        self.uv = torch.zeros((self.ch, self.cw, 2), dtype=dt, device=device) if layout else None
+
+    def tensors(self):
+        """(Y (h, w), UV (ch, cw, 2) or None)."""
+        return self.y, self.uv
+
+    def image(self):
+        """The MiScaledImage over the tensors."""
+        im = MiScaledImage()
+        im.w, im.h, im.bpc = self.w, self.h, self.bpc
+        pxb = 1 if self.bpc == 8 else 2
+        im.data[0], im.stride[0] = self.y.data_ptr(), self.w * pxb
+        if self.uv is not None:
+            im.data[1], im.stride[1] = self.uv.data_ptr(), 2 * self.cw * pxb
+        if self.crop is not None:
+            im.crop_x, im.crop_y, im.crop_w, im.crop_h = self.crop
+        return im
+
+    def numpy(self):
+        """Host copies of the tensors as unsigned samples: [Y] or [Y, UV]."""
+        out = []
+        for t in self.tensors():
+            if t is not None:
+                a = t.cpu().numpy()
+                out.append(a.view("<u2") if self.bpc > 8 else a)
+        return out
+
+
+def display_scaled(ctx, frame, images, color=None, fg=None, stream=None):
+    """Enqueue mi_display_scaled: `frame` (a device Frame or a MiPicture) cropped, resized and
+    converted to each rung's depth into `images`, 1 to 8 ScaledImage or MiScaledImage (or one of
+    them on its own), semi-planar at the frame's own subsampling, in one call: film grain (`fg`: a
+    MiFilmGrainData or a make_fg_params dict) is applied once and every rung reads the grained
+    picture. color: a MiColorInfo or None; only its chr is read (the 4:2:0 chroma siting, of the
+    source and of the output). Raises MiError on a negative return."""
+    from .frame import _stream_ptr, film_grain_data
+    src = frame if isinstance(frame, MiPicture) else frame.picture()
+    if isinstance(images, (ScaledImage, MiScaledImage)):
+        images = [images]
+    ims = (MiScaledImage * max(len(images), 1))()
+    for i, image in enumerate(images):
+        ims[i] = image if isinstance(image, MiScaledImage) else image.image()
+    if fg is not None and not isinstance(fg, MiFilmGrainData):
+        fg = film_grain_data(fg)
+    check(lib().mi_display_scaled(ctx.h, ctypes.byref(src), ims, len(images),
+                                  ctypes.byref(color) if color is not None else None,
+                                  ctypes.byref(fg) if fg is not None else None, _stream_ptr(stream)),
+          "mi_display_scaled")
+
+
 __all__ = ["DisplayImage", "MiDisplayImage", "MiColorInfo", "display_picture", "FORMATS",
+           "MiScaledImage", "ScaledImage", "display_scaled", "even_crop",
            "OUT_SEMIPLANAR", "OUT_RGB_PLANAR", "OUT_RGBA_PACKED",
            "MiTensorImage", "tensor_image", "display_tensor", "T_U8", "T_F16", "T_BF16", "T_F32",
            "MiToneMap", "ToneMap", "tonemap_tables"]

@@ -245,6 +245,53 @@ def decode_to_batches(ctx, data, size, batch=8, dtype=None, channels_last=False,
         yield state["tensor"][:len(state["colors"])], state["colors"]
 
 
+def decode_to_ladder(ctx, data, sizes, bpc=None, fit="stretch", apply_grain=True, stream=None, inloop_filters=14,
+                     threads=1, operating_point=0, all_layers=True, decode_frame_type="all", frame_size_limit=0):
+    """Decode a stream on the device and yield, per shown picture in output order, (event, rungs):
+    the decoder event that showed it and a list with one (Y, UV) pair of device tensors per entry
+    of `sizes` ((W, H) luma sizes), the picture as semi-planar YUV at the stream's own subsampling
+    through one mi_display_scaled call (rav1d_amd.display.display_scaled): Y is (H, W), UV is
+    (ch, cw, 2), None for 4:0:0. bpc: the depth of every rung (8, 10 or 12; None keeps the
+    stream's); uint8 at 8 bits, else 16-bit words MSB-aligned in int16 storage. fit: fit_crop's,
+    per size, moved onto the chroma grid (rav1d_amd.display.even_crop); pictures of different sizes
+    in a stream each get their own crops. Film grain is applied once per picture when the frame
+    carries it and apply_grain is set; the chroma siting is the sequence header's. Every tensor is
+    a fresh allocation the caller owns, filled by work enqueued on `stream` (synchronise it, or
+    stay on it, before reading). The other settings are decode_ivf's."""
+    from .av1dec import MiColorInfo
+    from .display import ScaledImage, display_scaled, even_crop
+    sizes = [(int(W), int(H)) for W, H in sizes]
+    if not 1 <= len(sizes) <= 8:
+        raise ValueError("1 to 8 sizes")
+    for W, H in sizes:
+        fit_crop(1, 1, W, H, fit)      # (an unknown fit fails before any decoding)
+    dec = Av1Decoder(threads, inloop_filters, operating_point, all_layers, decode_frame_type, frame_size_limit)
+    pics = {}
+
+    def consume():
+        for ev in dec.events():
+            if ev.frame:
+                pics[ev.pic_id] = run_frame(ctx, ev.frame.contents, stream, _refs(pics, ev))
+                frame_end(ctx, stream)
+            if ev.show_pic >= 0:
+                src = pics[ev.show_pic].output()
+                color = MiColorInfo(*ev.color.astuple())
+                images = [ScaledImage(W, H, src.bpc if bpc is None else bpc, src.layout,
+                                      even_crop(fit_crop(src.w, src.h, W, H, fit), src.w, src.h, src.layout))
+                          for W, H in sizes]
+                display_scaled(ctx, src, images, color, ev.fg if (ev.fg_present and apply_grain) else None, stream)
+                yield ev, [im.tensors() for im in images]
+            for i in range(ev.n_release):
+                pics.pop(ev.release[i], None)
+
+    for tu in stream_units(data):
+        dec.send(tu)
+        yield from consume()
+    dec.drain()
+    yield from consume()
+    frame_end(ctx, stream)
+
+
 _extra_lanes = {}
 
 
