@@ -525,12 +525,17 @@ template <bool TM> using ToneParam = typename ToneSel<TM>::type;
 // RGB formats only; the destination samples are u8 at dst_bpc 8, else u16
 int launch_display_tm(const DisplayArgs &a, const ToneArgs &tm, int bpc, int dst_bpc, int format, hipStream_t s);
 
-// tensor output (tensor.hip): crop, separable triangle resize in 18-bit integers, finish to
+// the separable triangle resize of the tensor and scaled outputs (resize.h): one axis of a tap
+// table, and the list of axes one launch of the taps kernel fills (a scaled call: up to 8 rungs of
+// luma x, luma y, chroma x, chroma y)
+constexpr int kTapAxes = 32;
+struct TapAxis { int n_in, n_out, phase, cap; int *tab; };   // phase 2: centred, 4: co-sited
+struct TapList { TapAxis ax[kTapAxes]; int n; };
+
+// tensor output (tensor.hip): crop, separable triangle resize (resize.h), finish to
 // u8 / f16 / bf16 / f32, of the R'G'B' picture DisplayArgs `d` describes (its source half only).
-// Scratch: `tab` holds per axis the first tap, the tap count and the taps (tap j of output o at
-// [j * n_out + o]); `mid` holds the horizontal pass's result, 3 x crop_h rows of mstride u16.
-constexpr int kTensorS = 18;      // fraction bits of a tap
-constexpr int kTensorSeg = 2048;  // source columns one workgroup of the horizontal pass holds
+// Scratch: `tab` holds the two axes' tap tables; `mid` holds the horizontal pass's result,
+// 3 x crop_h rows of mstride u16.
 struct TensorArgs {
     DisplayArgs d;
     int cx, cy, cw, ch;           // the crop, luma pixels
@@ -547,13 +552,13 @@ struct TensorArgs {
     float scale[3], bias[3];
 };
 enum { kTensorCHW = 0, kTensorHWC = 1, kTensorAny = 2 };
-// tm: the colour-volume stage in the tile fill of the horizontal pass, or nullptr
-int launch_tensor(const TensorArgs &t, int bpc, int order, bool taps, hipStream_t s, const ToneArgs *tm = nullptr);
+// the two passes (the tap tables are in place); tm: the colour-volume stage in the tile fill of
+// the horizontal pass, or nullptr
+int launch_tensor(const TensorArgs &t, int bpc, int order, hipStream_t s, const ToneArgs *tm = nullptr);
 
 // scaled semi-planar output (scaled.hip): per rung, the luma plane and the U / V pair each cropped,
-// resized (the separable 18-bit triangle filter of the tensor output, with the chroma siting in
-// the taps), converted to the rung's depth and stored as Y and interleaved UV.
-constexpr int kScaledSeg = 2048;  // source columns one workgroup of the horizontal pass holds
+// resized (resize.h, with the chroma siting in the taps), converted to the rung's depth and stored
+// as Y and interleaved UV.
 struct ScaledPlane {              // luma (1 channel) or chroma (2 channels: U, V)
     const uint8_t *src[2];
     int64_t sstride;
@@ -578,9 +583,6 @@ struct ScaledArgs {
     int up;                       // left shift after it: (d - s when d > s) + (16 - d when d > 8)
     int maxd;                     // Md
 };
-struct ScaledAxis { int n_in, n_out, phase, cap; int *tab; };   // phase 2: centred, 4: co-sited
-struct ScaledTaps { ScaledAxis ax[32]; int n; };
-int launch_scaled_taps(const ScaledTaps &t, hipStream_t s);
 int launch_scaled(const ScaledArgs &a, int src_bpc, int dst_bpc, hipStream_t s);
 
 // ---- per-call (table-compatible) entry points: single-block kernels ----

@@ -3,7 +3,48 @@
 #pragma once
 #include "common.h"
 
+#include <cstring>
 #include <vector>
+
+// The device scratch of a resized output (mi_display_tensor, mi_display_scaled): the tap tables of
+// a list of axes, then the horizontal pass's result, in one allocation that is replaced only when
+// a call needs more. The tables depend on the list alone, and so does where they lie: a call with
+// the list of the one before it on this context (every picture of a stream, as a rule) reuses
+// them, ordered behind their launch on the context's stream.
+struct MiResizeScratch {
+    uint8_t *p = nullptr;
+    size_t bytes = 0;
+    // the axis count, then n_in, n_out, phase per axis of the tables held (all 0: none)
+    int key[1 + 3 * mi::kTapAxes] = {0};
+    // Before any launch of the call: at least `need` bytes, or false with nothing held. Growing
+    // loses the tables.
+    bool ensure(size_t need) {
+        if (need <= bytes) return true;
+        if (p) (void)hipFree(p);   // (waits for the work that reads it)
+        p = nullptr;
+        bytes = 0;
+        forget();
+        if (hipMalloc(&p, need) != hipSuccess) return false;
+        bytes = need;
+        return true;
+    }
+    bool holds(const mi::TapList &t) const {
+        int k[1 + 3 * mi::kTapAxes];
+        fill(t, k);
+        return memcmp(k, key, sizeof(key)) == 0;
+    }
+    // before the launches that write or read the tables, and after all of them were enqueued
+    // without error: a call that fails in between leaves no tables to reuse
+    void forget() { memset(key, 0, sizeof(key)); }
+    void keep(const mi::TapList &t) { fill(t, key); }
+
+  private:
+    static void fill(const mi::TapList &t, int *k) {
+        memset(k, 0, sizeof(key));
+        k[0] = t.n;
+        for (int a = 0; a < t.n; a++) k[1 + 3 * a] = t.ax[a].n_in, k[2 + 3 * a] = t.ax[a].n_out, k[3 + 3 * a] = t.ax[a].phase;
+    }
+};
 
 struct MiCtx {
     int device = 0;
@@ -17,17 +58,9 @@ struct MiCtx {
     // the geometry of the shown picture, replaced only when a picture needs more)
     uint8_t *disp_fg = nullptr;
     size_t disp_fg_bytes = 0;
-    // mi_display_tensor: the tap tables and the horizontal pass's result (one allocation,
-    // replaced only when a call needs more)
-    uint8_t *tens = nullptr;
-    size_t tens_bytes = 0;
-    int tens_geom[4] = {0, 0, 0, 0};   // crop w, out w, crop h, out h of the tap tables it holds (0: none)
-    // mi_display_scaled: its own tap tables and horizontal result (one allocation, replaced only
-    // when a call needs more); scal_key: the rung count and per rung the plane extents and tap
-    // phases of the tables it holds (all 0: none)
-    uint8_t *scal = nullptr;
-    size_t scal_bytes = 0;
-    int scal_key[1 + 8 * 10] = {0};
+    // mi_display_tensor and mi_display_scaled: a scratch each, so that alternating calls of the
+    // two keep their tables
+    MiResizeScratch tens, scal;
     // mi_display_*_tm: the device tables (lut_out, then lut_in) of the key `tone_key` (*tm with
     // the peaks zeroed for sources that do not read them, pri, trc, source bpc), their matrix, and
     // two pinned staging buffers used in turn; `tone_ev[i]` marks when buffer i may be rewritten
@@ -96,8 +129,8 @@ struct MiCtx {
         if (fg_scaling) (void)hipFree(fg_scaling);
         if (fg_offsets) (void)hipFree(fg_offsets);
         if (disp_fg) (void)hipFree(disp_fg);
-        if (tens) (void)hipFree(tens);
-        if (scal) (void)hipFree(scal);
+        if (tens.p) (void)hipFree(tens.p);
+        if (scal.p) (void)hipFree(scal.p);
         if (tone_dev) (void)hipFree(tone_dev);
         for (int i = 0; i < 2; i++) {
             if (tone_ev[i]) (void)hipEventDestroy(tone_ev[i]);

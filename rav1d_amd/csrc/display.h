@@ -1,7 +1,10 @@
-// display.h — what display.hip (mi_display_picture) and tensor.hip (mi_display_tensor) share: the
-// host side of the R'G'B' conversion (colour checks and 14-bit coefficients, the grained scratch
-// picture, the source half of DisplayArgs) and its device side (vector loads of a plane run, the
-// integer chroma upsampler, the matrix), so both entries compute the same picture.
+// display.h — what the device outputs share. All of them (display.hip mi_display_picture,
+// tensor.hip mi_display_tensor, scaled.hip mi_display_scaled): the checks of the source picture
+// and of a crop, the film-grain step, vector loads of a plane run. The R'G'B' outputs
+// (mi_display_picture, mi_display_tensor): the host side of the conversion (colour checks and
+// 14-bit coefficients, the source half of DisplayArgs) and its device side (the integer chroma
+// upsampler, the matrix, the colour-volume stage), so both compute the same picture. The resize of
+// the tensor and scaled outputs is resize.h.
 #pragma once
 #include "mi_av1out.h"
 #include "ctx.h"
@@ -11,13 +14,25 @@ namespace mi {
 constexpr int kDispS = 14;   // fixed-point fraction bits of the matrix
 
 // ---- host (display.hip) ----
+// The source picture `in` (not NULL): plane pointers, extents in 1..65536, layout, bpc, strides
+// present (display_check_picture), and strides that hold a row (display_check_strides; after the
+// former). 0 or -EINVAL.
+int display_check_picture(const MiPicture *in);
+int display_check_strides(const MiPicture *in);
+// The crop rectangle of an output in luma pixels: the whole picture when crop_w and crop_h are
+// both 0, else the rectangle, which must lie inside the picture. 0 or -EINVAL.
+int display_crop(const MiPicture *in, int crop_x, int crop_y, int crop_w, int crop_h, int &cx, int &cy, int &cw, int &ch);
+// The film-grain step of a call with grain: points `src` (a copy of `in`) at the context's
+// grained scratch picture in the geometry of `in`, allocating or growing it (-ENOMEM with
+// last_error set; nothing launched), then mi_film_grain_frame into it on `stream` (its errors).
+// `color` may be NULL.
+int display_grain(MiCtx *ctx, const MiPicture *in, MiPicture *src, const MiFilmGrainData *fg, const MiColorInfo *color,
+                  void *stream);
+inline bool aligned_to(const void *p, ptrdiff_t stride, uintptr_t n) { return (((uintptr_t)p | (uintptr_t)stride) & (n - 1)) == 0; }
 // The colour rules of the RGB formats: -EINVAL for NULL `color`, mtrx 2 or reserved, a range that
 // is not 0 / 1, identity without 4:4:4; -ENOTSUP for matrices 8 and 10-14; else 0 with a.identity
 // or a.yo / a.ky / a.crv / a.cbu / a.cgu / a.cgv set. No device work.
 int display_color(const MiPicture *in, const MiColorInfo *color, DisplayArgs &a);
-// Point `src` (a copy of `in`) at the context's grained scratch picture in the geometry of `in`,
-// allocating or growing it: 0 or -ENOMEM (with last_error set). No launch.
-int display_grain_picture(MiCtx *ctx, const MiPicture *in, MiPicture *src);
 // The source half of DisplayArgs: planes, strides, vector-load flags, sizes, siting, H and M.
 void display_source(const MiPicture &src, const MiColorInfo *color, DisplayArgs &a);
 

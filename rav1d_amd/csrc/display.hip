@@ -243,9 +243,32 @@ int matrix_k(int mtrx, double *kr, double *kb) {
 
 int round_fix(double v) { return (int)floor(v * (double)(1 << kDispS) + 0.5); }
 
-bool aligned16(const void *p, ptrdiff_t stride) { return (((uintptr_t)p | (uintptr_t)stride) & 15) == 0; }
-
 }  // namespace
+
+int display_check_picture(const MiPicture *in) {
+    if (!in->data[0] || in->w <= 0 || in->h <= 0 || in->w > 65536 || in->h > 65536 || in->layout < 0 || in->layout > 3 ||
+        (in->bpc != 8 && in->bpc != 10 && in->bpc != 12) || in->stride[0] <= 0)
+        return -EINVAL;
+    if (in->layout && (!in->data[1] || !in->data[2] || in->stride[1] <= 0)) return -EINVAL;
+    return 0;
+}
+
+int display_check_strides(const MiPicture *in) {
+    const int pxb = in->bpc == 8 ? 1 : 2, ss_hor = in->layout == 1 || in->layout == 2;
+    if ((int64_t)in->stride[0] < (int64_t)in->w * pxb ||
+        (in->layout && (int64_t)in->stride[1] < (int64_t)((in->w + ss_hor) >> ss_hor) * pxb))
+        return -EINVAL;
+    return 0;
+}
+
+int display_crop(const MiPicture *in, int crop_x, int crop_y, int crop_w, int crop_h, int &cx, int &cy, int &cw, int &ch) {
+    cx = 0, cy = 0, cw = in->w, ch = in->h;
+    if (crop_w || crop_h) {
+        cx = crop_x, cy = crop_y, cw = crop_w, ch = crop_h;
+        if (cx < 0 || cy < 0 || cw < 1 || ch < 1 || (int64_t)cx + cw > in->w || (int64_t)cy + ch > in->h) return -EINVAL;
+    }
+    return 0;
+}
 
 int display_color(const MiPicture *in, const MiColorInfo *color, DisplayArgs &a) {
     if (!color || color->mtrx == 2 || (color->range != 0 && color->range != 1)) return -EINVAL;
@@ -268,7 +291,8 @@ int display_color(const MiPicture *in, const MiColorInfo *color, DisplayArgs &a)
     return 0;
 }
 
-int display_grain_picture(MiCtx *ctx, const MiPicture *in, MiPicture *src) {
+int display_grain(MiCtx *ctx, const MiPicture *in, MiPicture *src, const MiFilmGrainData *fg, const MiColorInfo *color,
+                  void *stream) {
     // the grained picture, in the geometry of `in`
     const int ss_ver = in->layout == 1;
     const size_t ah = ((size_t)in->h + 127) & ~(size_t)127;
@@ -284,14 +308,14 @@ int display_grain_picture(MiCtx *ctx, const MiPicture *in, MiPicture *src) {
     src->data[0] = ctx->disp_fg;
     src->data[1] = in->layout ? ctx->disp_fg + ybytes : nullptr;
     src->data[2] = in->layout ? ctx->disp_fg + ybytes + cbytes : nullptr;
-    return 0;
+    return mi_film_grain_frame(ctx, in, src, fg, color && color->mtrx == 0, stream);
 }
 
 void display_source(const MiPicture &src, const MiColorInfo *color, DisplayArgs &a) {
     const int ss_hor = src.layout == 1 || src.layout == 2, ss_ver = src.layout == 1;
     for (int p = 0; p < (src.layout ? 3 : 1); p++) {
         a.src[p] = (const uint8_t *)src.data[p];
-        if (aligned16(src.data[p], src.stride[p ? 1 : 0])) a.svec |= 1 << p;
+        if (aligned_to(src.data[p], src.stride[p ? 1 : 0], 16)) a.svec |= 1 << p;
     }
     a.sstride[0] = src.stride[0];
     a.sstride[1] = src.stride[1];
@@ -314,17 +338,15 @@ namespace {
 // mi_display_picture (tone false; tm not read) and mi_display_picture_tm (tone true)
 int display_picture(MiCtx *ctx, const MiPicture *in, const MiDisplayImage *out, const MiColorInfo *color, bool tone,
                     const MiToneMap *tm, const MiFilmGrainData *fg, void *stream) {
-    if (!in || !out || !in->data[0] || in->w <= 0 || in->h <= 0 || in->w > 65536 || in->h > 65536 ||
-        in->layout < 0 || in->layout > 3 || (in->bpc != 8 && in->bpc != 10 && in->bpc != 12) || in->stride[0] <= 0)
-        return -EINVAL;
-    if (in->layout && (!in->data[1] || !in->data[2] || in->stride[1] <= 0)) return -EINVAL;
+    if (!in || !out) return -EINVAL;
+    if (int e = mi::display_check_picture(in)) return e;
     if (out->w != in->w || out->h != in->h) return -EINVAL;
     // the output depth: the source's, or with the colour-volume stage dst_bpc (checked below)
     if (tone ? out->bpc != 8 && out->bpc != 10 && out->bpc != 12 : out->bpc != in->bpc) return -EINVAL;
     if (out->format != MI_OUT_SEMIPLANAR && out->format != MI_OUT_RGB_PLANAR && out->format != MI_OUT_RGBA_PACKED)
         return -EINVAL;
     if (tone && out->format == MI_OUT_SEMIPLANAR) return -ENOTSUP;
-    const int pxb = in->bpc == 8 ? 1 : 2, ss_hor = in->layout == 1 || in->layout == 2, ss_ver = in->layout == 1;
+    const int ss_hor = in->layout == 1 || in->layout == 2, ss_ver = in->layout == 1;
     const int dpxb = out->bpc == 8 ? 1 : 2;   // bytes of a destination sample
     const int cw = (in->w + ss_hor) >> ss_hor, ch = (in->h + ss_ver) >> ss_ver;
     // destination planes and the samples a row of each holds
@@ -335,8 +357,7 @@ int display_picture(MiCtx *ctx, const MiPicture *in, const MiDisplayImage *out, 
         if (!out->data[p] || out->stride[p] < samples * dpxb) return -EINVAL;
         if (((uintptr_t)out->data[p] | (uintptr_t)out->stride[p]) & (uintptr_t)(dpxb - 1)) return -EINVAL;
     }
-    if ((int64_t)in->stride[0] < (int64_t)in->w * pxb || (in->layout && (int64_t)in->stride[1] < (int64_t)cw * pxb))
-        return -EINVAL;
+    if (int e = mi::display_check_strides(in)) return e;
 
     mi::DisplayArgs a;
     memset(&a, 0, sizeof(a));
@@ -353,16 +374,14 @@ int display_picture(MiCtx *ctx, const MiPicture *in, const MiDisplayImage *out, 
     if (tone)
         if (int e = mi::tone_prepare(ctx, tm, color, in->bpc, (hipStream_t)stream, ta)) return e;
     MiPicture src = *in;
-    if (fg) {
-        if (int e = mi::display_grain_picture(ctx, in, &src)) return e;
-        if (int e = mi_film_grain_frame(ctx, in, &src, fg, color && color->mtrx == 0, stream)) return e;
-    }
+    if (fg)
+        if (int e = mi::display_grain(ctx, in, &src, fg, color, stream)) return e;
 
     mi::display_source(src, color, a);
     for (int p = 0; p < ndst; p++) {
         a.dst[p] = (uint8_t *)out->data[p];
         a.dstride[p] = out->stride[p];
-        if (mi::aligned16(out->data[p], out->stride[p])) a.dvec |= 1 << p;
+        if (mi::aligned_to(out->data[p], out->stride[p], 16)) a.dvec |= 1 << p;
     }
     a.shift = out->format == MI_OUT_SEMIPLANAR && in->bpc > 8 ? 16 - in->bpc : 0;
     a.chunks = (in->w + 7) >> 3;

@@ -1,124 +1,64 @@
 // scaled.hip — mi_display_scaled (include/mi_av1out.h): a shown picture as cropped, resized
 // semi-planar YUV at a chosen depth, up to 8 rungs of a transcode ladder per call. The resize is
-// the separable 18-bit triangle filter of tensor.hip run in the YUV domain: every plane on its own,
+// the separable 18-bit triangle filter of resize.h run in the YUV domain: every plane on its own,
 // at its own resolution, the chroma siting in the taps (a co-sited axis takes the (4o+1) / (4i+1)
 // form of the formula), so there is no chroma upsample and no matrix.
 //
 // Launches on the caller's stream, all scratch in one context-owned allocation of its own (the
 // tensor output's tables are never these):
-//   scaled_taps_kernel   one lane per output position of every axis of every rung (up to four
-//                        axes per rung: luma x, luma y, chroma x, chroma y): first tap, tap count
-//                        and taps; skipped when the scratch holds the tables of the same rungs;
+//   taps_kernel          (resize.h) the tap tables of every axis of every rung (up to four axes
+//                        per rung: luma x, luma y, chroma x, chroma y); skipped when the scratch
+//                        holds the tables of the same rungs;
 //   per rung:
 //   scaled_h_kernel      one workgroup per (plane row of the crop, segment of output columns); the
 //                        U and V rows of a chroma row go together. The lanes stage the run of the
 //                        row the segment's taps reach in LDS (display.h load_run: one vector per 8
 //                        samples), then a lane owns output columns and filters from LDS into `mid`
-//                        (u16). The segment is sized on the host so that the taps fit kScaledSeg.
+//                        (u16). The segment is sized on the host so that the taps fit kTensorSeg.
 //                        Rows outside the crop are not read;
 //   scaled_v_kernel      a lane owns 4 adjacent output columns of one output row (of U and V
 //                        both): per tap one 8-byte load of `mid` per channel and a wave-uniform
 //                        weight; then the depth conversion and the store, Y as one vector of 4
 //                        samples, UV as one vector of 4 interleaved pairs, where the pointer and
 //                        the stride allow, else sample by sample.
-// Both passes run every slot of the tap table (zero weights past an output's own taps), as the
-// tensor output's do. Luma and chroma of a rung share each launch: the first blocks are luma's.
+// Luma and chroma of a rung share each launch: the first blocks are luma's.
 #include <algorithm>
 #include <cerrno>
 #include <cstring>
 
-#include "display.h"
+#include "resize.h"
 
 namespace mi {
 namespace {
 
-// ---- taps ----
-// Output o of an axis n_in -> n_out with phase P (2: centred, 4: co-sited): Rr = P max(n_in, n_out),
-// C = (P o + 1) n_in, wt_i = Rr - |C - (P i + 1) n_out| over every integer i, taps where wt_i > 0.
-__device__ __forceinline__ int64_t sited_wt(int64_t rr, int64_t c, int64_t n_out, int64_t ph, int64_t i) {
-    const int64_t d = c - (ph * i + 1) * n_out;
-    return rr - (d < 0 ? -d : d);
-}
-
-__device__ void sited_taps(const ScaledAxis &ax, int o) {
-    const int n_in = ax.n_in, n_out = ax.n_out, cap = ax.cap;
-    int *start = ax.tab, *count = start + n_out, *k = count + n_out;
-    const int64_t ph = ax.phase, rr = ph * (int64_t)max(n_in, n_out), c = (ph * (int64_t)o + 1) * n_in, np = ph * (int64_t)n_out;
-    // floor((C - Rr) / P n_out) - 1 is left of the support: (P i + 1) n_out <= C - Rr there
-    const int64_t a = c - rr;
-    int64_t i0 = (a >= 0 ? a / np : -((-a + np - 1) / np)) - 1;
-    while (sited_wt(rr, c, n_out, ph, i0) <= 0) i0++;
-    int n = 0, best = 0;
-    int64_t wsum = 0, wbest = 0;
-    while (n < cap) {
-        const int64_t w = sited_wt(rr, c, n_out, ph, i0 + n);
-        if (w <= 0) break;
-        wsum += w;
-        if (w > wbest) {   // the first tap with the largest weight
-            wbest = w;
-            best = n;
-        }
-        n++;
-    }
-    int64_t ksum = 0;
-    for (int j = 0; j < n; j++) {
-        const int64_t kj = ((sited_wt(rr, c, n_out, ph, i0 + j) << kTensorS) + wsum / 2) / wsum;
-        k[(int64_t)j * n_out + o] = (int)kj;
-        ksum += kj;
-    }
-    k[(int64_t)best * n_out + o] += (int)(((int64_t)1 << kTensorS) - ksum);
-    for (int j = n; j < cap; j++) k[(int64_t)j * n_out + o] = 0;
-    start[o] = (int)i0;
-    count[o] = n;
-}
-
-__global__ __launch_bounds__(256) void scaled_taps_kernel(const ScaledTaps t) {
-    int i = blockIdx.x * 256 + threadIdx.x;
-    for (int a = 0; a < t.n; a++) {
-        if (i < t.ax[a].n_out) {
-            sited_taps(t.ax[a], i);
-            return;
-        }
-        i -= t.ax[a].n_out;
-    }
-}
-
 // ---- horizontal pass ----
 template <typename Px, int NC>
-__device__ __forceinline__ void h_pass(const ScaledPlane &p, int r, int seg, uint16_t (&tile)[2][kScaledSeg]) {
+__device__ __forceinline__ void h_pass(const ScaledPlane &p, int r, int seg, uint16_t (&tile)[2][kTensorSeg]) {
     const int o0 = seg * p.ob, o1 = min(o0 + p.ob, p.ow) - 1;
     const int *hs = p.htab, *hc = hs + p.ow, *hk = hc + p.ow;
     // plane columns [lo, hi) the segment's taps read, inside the crop whatever the tables hold;
     // the tile starts at the 8-column run of lo
     const int lo = p.px + min(max(hs[o0], 0), p.pcw - 1), hi = p.px + min(max(hs[o1] + hc[o1], 1), p.pcw);
     const int xa = lo & ~7, x0 = xa + 8 * (int)threadIdx.x;
-    if (x0 < hi && x0 - xa + 8 <= kScaledSeg) {
+    if (x0 < hi && x0 - xa + 8 <= kTensorSeg) {
 #pragma unroll
         for (int c = 0; c < NC; c++) {
             int v[8];
             load_run<Px, 8>(p.src[c] + (int64_t)(p.py + r) * p.sstride, x0, p.pw, (p.svec >> c) & 1, v);
-            *reinterpret_cast<uint4 *>(&tile[c][x0 - xa]) =
-                make_uint4((uint32_t)v[0] | ((uint32_t)v[1] << 16), (uint32_t)v[2] | ((uint32_t)v[3] << 16),
-                           (uint32_t)v[4] | ((uint32_t)v[5] << 16), (uint32_t)v[6] | ((uint32_t)v[7] << 16));
+            *reinterpret_cast<uint4 *>(&tile[c][x0 - xa]) = pack8(v);
         }
     }
     __syncthreads();
-    // crop column clamp(s + j, 0, pcw - 1) as a tile column, held inside the tile (the outer
-    // bounds bind only for zero-weight slots: the host sizes ob so that an output's taps fit)
-    const int lo_i = max(p.px - xa, 0), hi_i = min(p.px - xa + p.pcw - 1, kScaledSeg - 1);
+    // the crop's columns as tile columns, held inside the tile
+    const int lo_i = max(p.px - xa, 0), hi_i = min(p.px - xa + p.pcw - 1, kTensorSeg - 1);
     for (int o = o0 + (int)threadIdx.x; o <= o1; o += 256) {
         const int base = hs[o] + p.px - xa;
         const int *k = hk + o;
         int acc[NC];
 #pragma unroll
-        for (int c = 0; c < NC; c++) acc[c] = 1 << (kTensorS - 1);
+        for (int c = 0; c < NC; c++) acc[c] = kTensorHalf;
 #pragma unroll 4
-        for (int j = 0; j < p.th; j++) {
-            const int idx = min(max(base + j, lo_i), hi_i);
-            const int kj = k[(int64_t)j * p.ow];
-#pragma unroll
-            for (int c = 0; c < NC; c++) acc[c] += kj * (int)tile[c][idx];
-        }
+        for (int j = 0; j < p.th; j++) h_tap<NC>(tile, base + j, lo_i, hi_i, k[(int64_t)j * p.ow], acc);
 #pragma unroll
         for (int c = 0; c < NC; c++)
             p.mid[((int64_t)c * p.pch + r) * p.mstride + o] = (uint16_t)(acc[c] >> kTensorS);
@@ -127,7 +67,7 @@ __device__ __forceinline__ void h_pass(const ScaledPlane &p, int r, int seg, uin
 
 template <typename Px>
 __global__ __launch_bounds__(256) void scaled_h_kernel(const ScaledArgs a) {
-    __shared__ __attribute__((aligned(16))) uint16_t tile[2][kScaledSeg];
+    __shared__ __attribute__((aligned(16))) uint16_t tile[2][kTensorSeg];
     const int r = blockIdx.x, seg = blockIdx.y;
     if (r < a.p[0].pch) {   // (block-uniform: every lane of a workgroup meets the barrier or none)
         if (seg < a.p[0].segs) h_pass<Px, 1>(a.p[0], r, seg, tile);
@@ -142,27 +82,18 @@ __device__ __forceinline__ void v_pass(const ScaledArgs &a, const ScaledPlane &p
     const int x0 = (xb * 256 + (int)threadIdx.x) * 4;
     if (x0 >= p.ow) return;
     const int *vs = p.vtab, *vk = vs + 2 * p.oh;
-    const int s = vs[oy];
     // (rows of mid are 16-byte aligned and x0 is a multiple of 4; columns past ow are padding)
+    const int s = vs[oy];
     const uint16_t *m = p.mid + x0;
     const int64_t plane = (int64_t)p.pch * p.mstride;
     int acc[NC][4];
 #pragma unroll
     for (int c = 0; c < NC; c++)
 #pragma unroll
-        for (int i = 0; i < 4; i++) acc[c][i] = 1 << (kTensorS - 1);
+        for (int i = 0; i < 4; i++) acc[c][i] = kTensorHalf;
 #pragma unroll 4
-    for (int j = 0; j < p.tv; j++) {
-        const int row = min(max(s + j, 0), p.pch - 1), k = vk[(int64_t)j * p.oh + oy];
-#pragma unroll
-        for (int c = 0; c < NC; c++) {
-            const uint2 q = *reinterpret_cast<const uint2 *>(m + c * plane + row * p.mstride);
-            acc[c][0] += k * (int)(q.x & 0xffff);
-            acc[c][1] += k * (int)(q.x >> 16);
-            acc[c][2] += k * (int)(q.y & 0xffff);
-            acc[c][3] += k * (int)(q.y >> 16);
-        }
-    }
+    for (int j = 0; j < p.tv; j++)
+        v_tap<NC>(m, plane, min(max(s + j, 0), p.pch - 1) * p.mstride, vk[(int64_t)j * p.oh + oy], acc);
     // samples in store order: Y0 .. Y3, or U0 V0 .. U3 V3
     uint32_t e[4 * NC];
 #pragma unroll
@@ -207,16 +138,7 @@ __global__ __launch_bounds__(256) void scaled_v_kernel(const ScaledArgs a) {
     }
 }
 
-bool aligned_to(const void *p, ptrdiff_t stride, uintptr_t n) { return (((uintptr_t)p | (uintptr_t)stride) & (n - 1)) == 0; }
-
 }  // namespace
-
-int launch_scaled_taps(const ScaledTaps &t, hipStream_t s) {
-    int64_t n = 0;
-    for (int a = 0; a < t.n; a++) n += t.ax[a].n_out;
-    scaled_taps_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(t);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
 
 int launch_scaled(const ScaledArgs &a, int src_bpc, int dst_bpc, hipStream_t s) {
     const bool chroma = a.nplanes > 1;
@@ -246,22 +168,15 @@ struct PlaneGeom {
     size_t htab, vtab, mid;   // byte offsets
 };
 
-int tap_cap(int n_in, int n_out) { return 2 * ((std::max(n_in, n_out) + n_out - 1) / n_out) + 1; }
-
 }  // namespace
 
 extern "C" int mi_display_scaled(MiCtx *ctx, const MiPicture *in, const MiScaledImage *outs, int n_outs,
                                  const MiColorInfo *color, const MiFilmGrainData *fg, void *stream) {
     if (!in || !outs || n_outs < 1 || n_outs > 8) return -EINVAL;
-    if (!in->data[0] || in->w <= 0 || in->h <= 0 || in->w > 65536 || in->h > 65536 || in->layout < 0 || in->layout > 3 ||
-        (in->bpc != 8 && in->bpc != 10 && in->bpc != 12) || in->stride[0] <= 0)
-        return -EINVAL;
-    if (in->layout && (!in->data[1] || !in->data[2] || in->stride[1] <= 0)) return -EINVAL;
-    const int pxb = in->bpc == 8 ? 1 : 2, sh = in->layout == 1 || in->layout == 2, sv = in->layout == 1;
+    if (int e = mi::display_check_picture(in)) return e;
+    if (int e = mi::display_check_strides(in)) return e;
+    const int sh = in->layout == 1 || in->layout == 2, sv = in->layout == 1;
     const int nplanes = in->layout ? 2 : 1;
-    if ((int64_t)in->stride[0] < (int64_t)in->w * pxb ||
-        (in->layout && (int64_t)in->stride[1] < (int64_t)((in->w + sh) >> sh) * pxb))
-        return -EINVAL;
 
     PlaneGeom g[8][2];
     for (int r = 0; r < n_outs; r++) {
@@ -276,14 +191,13 @@ extern "C" int mi_display_scaled(MiCtx *ctx, const MiPicture *in, const MiScaled
             if ((int64_t)o.stride[p] < row || o.stride[p] % es) return -EINVAL;
             if ((uintptr_t)o.data[p] % (uintptr_t)es) return -EINVAL;
         }
-        int cx = 0, cy = 0, cw = in->w, ch = in->h;
-        if (o.crop_w || o.crop_h) {
-            cx = o.crop_x, cy = o.crop_y, cw = o.crop_w, ch = o.crop_h;
-            if (cx < 0 || cy < 0 || cw < 1 || ch < 1 || (int64_t)cx + cw > in->w || (int64_t)cy + ch > in->h) return -EINVAL;
-            if ((sh && (cx & 1)) || (sv && (cy & 1))) return -EINVAL;
-            if (sh && (cw & 1) && cx + cw != in->w) return -EINVAL;
-            if (sv && (ch & 1) && cy + ch != in->h) return -EINVAL;
-        }
+        int cx, cy, cw, ch;
+        if (int e = mi::display_crop(in, o.crop_x, o.crop_y, o.crop_w, o.crop_h, cx, cy, cw, ch)) return e;
+        // on the chroma grid: an even origin, and an odd extent only up to the picture's edge
+        // (the whole picture passes)
+        if ((sh && (cx & 1)) || (sv && (cy & 1))) return -EINVAL;
+        if (sh && (cw & 1) && cx + cw != in->w) return -EINVAL;
+        if (sv && (ch & 1) && cy + ch != in->h) return -EINVAL;
         g[r][0] = PlaneGeom{cx, cy, cw, ch, o.w, o.h, 2, 2, 0, 0, 0, 0, 0, 0};
         g[r][1] = PlaneGeom{cx >> sh, cy >> sv, (cw + sh) >> sh, (ch + sv) >> sv, ocw, och, sh ? 4 : 2, 0, 0, 0, 0, 0, 0, 0};
         for (int p = 0; p < nplanes; p++)
@@ -293,19 +207,16 @@ extern "C" int mi_display_scaled(MiCtx *ctx, const MiPicture *in, const MiScaled
     if (chr < 0 || chr > 2) return -EINVAL;
     if (!ctx) return -EINVAL;
 
-    // the scratch: every rung's tables (they stay while the key stays), then one `mid` the rungs
+    // the scratch: every rung's tables (they stay while the axes stay), then one `mid` the rungs
     // use in turn (they are ordered on the stream)
-    int key[1 + 8 * 10];
-    memset(key, 0, sizeof(key));
-    key[0] = n_outs;
     size_t tab_bytes = 0, mid_bytes = 0;
     for (int r = 0; r < n_outs; r++) {
         g[r][1].phy = sv && chr == 2 ? 4 : 2;
         size_t mid = 0;
         for (int p = 0; p < nplanes; p++) {
             PlaneGeom &q = g[r][p];
-            q.th = tap_cap(q.pcw, q.ow);
-            q.tv = tap_cap(q.pch, q.oh);
+            q.th = mi::tap_cap(q.pcw, q.ow);
+            q.tv = mi::tap_cap(q.pch, q.oh);
             q.mstride = ((int64_t)q.ow + 7) & ~(int64_t)7;
             q.htab = tab_bytes;
             tab_bytes += (size_t)(q.th + 2) * q.ow * sizeof(int);
@@ -313,45 +224,29 @@ extern "C" int mi_display_scaled(MiCtx *ctx, const MiPicture *in, const MiScaled
             tab_bytes += (size_t)(q.tv + 2) * q.oh * sizeof(int);
             q.mid = mid;
             mid += (size_t)(p ? 2 : 1) * q.pch * q.mstride * sizeof(uint16_t);
-            int *k = key + 1 + 10 * r + 4 * p;
-            k[0] = q.pcw, k[1] = q.ow, k[2] = q.pch, k[3] = q.oh;
         }
-        key[1 + 10 * r + 8] = g[r][1].phx;
-        key[1 + 10 * r + 9] = g[r][1].phy;
         mid_bytes = std::max(mid_bytes, mid);
     }
     tab_bytes = (tab_bytes + 255) & ~(size_t)255;
 
     // allocations first: a call that fails has launched nothing
-    if (tab_bytes + mid_bytes > ctx->scal_bytes) {
-        if (ctx->scal) (void)hipFree(ctx->scal);   // (waits for the work that reads it)
-        ctx->scal = nullptr;
-        ctx->scal_bytes = 0;
-        memset(ctx->scal_key, 0, sizeof(ctx->scal_key));
-        if (hipMalloc(&ctx->scal, tab_bytes + mid_bytes) != hipSuccess) return ctx->last_error = -ENOMEM;
-        ctx->scal_bytes = tab_bytes + mid_bytes;
-    }
-    // The tables depend on the key alone, and so does where they lie: a call with the rungs of
-    // the one before it on this context reuses them, ordered behind their launch on the stream.
-    const bool taps = memcmp(key, ctx->scal_key, sizeof(key)) != 0;
+    MiResizeScratch &sc = ctx->scal;
+    if (!sc.ensure(tab_bytes + mid_bytes)) return ctx->last_error = -ENOMEM;
+    mi::TapList tl;
+    memset(&tl, 0, sizeof(tl));
+    for (int r = 0; r < n_outs; r++)
+        for (int p = 0; p < nplanes; p++) {
+            const PlaneGeom &q = g[r][p];
+            tl.ax[tl.n++] = mi::TapAxis{q.pcw, q.ow, q.phx, q.th, (int *)(sc.p + q.htab)};
+            tl.ax[tl.n++] = mi::TapAxis{q.pch, q.oh, q.phy, q.tv, (int *)(sc.p + q.vtab)};
+        }
+    const bool taps = !sc.holds(tl);
     MiPicture src = *in;
-    if (fg) {
-        if (int e = mi::display_grain_picture(ctx, in, &src)) return e;
-        if (int e = mi_film_grain_frame(ctx, in, &src, fg, color && color->mtrx == 0, stream)) return e;
-    }
+    if (fg)
+        if (int e = mi::display_grain(ctx, in, &src, fg, color, stream)) return e;
 
-    memset(ctx->scal_key, 0, sizeof(ctx->scal_key));
-    if (taps) {
-        mi::ScaledTaps t;
-        memset(&t, 0, sizeof(t));
-        for (int r = 0; r < n_outs; r++)
-            for (int p = 0; p < nplanes; p++) {
-                const PlaneGeom &q = g[r][p];
-                t.ax[t.n++] = mi::ScaledAxis{q.pcw, q.ow, q.phx, q.th, (int *)(ctx->scal + q.htab)};
-                t.ax[t.n++] = mi::ScaledAxis{q.pch, q.oh, q.phy, q.tv, (int *)(ctx->scal + q.vtab)};
-            }
-        if (mi::launch_scaled_taps(t, (hipStream_t)stream)) return ctx->last_error = -EIO;
-    }
+    sc.forget();
+    if (taps && mi::launch_taps(tl, (hipStream_t)stream)) return ctx->last_error = -EIO;
     for (int r = 0; r < n_outs; r++) {
         const MiScaledImage &o = outs[r];
         mi::ScaledArgs a;
@@ -371,15 +266,12 @@ extern "C" int mi_display_scaled(MiCtx *ctx, const MiPicture *in, const MiScaled
             sp.sstride = src.stride[p];
             sp.pw = p ? (in->w + sh) >> sh : in->w;
             sp.px = q.px, sp.py = q.py, sp.pcw = q.pcw, sp.pch = q.pch, sp.ow = q.ow, sp.oh = q.oh;
-            sp.htab = (const int *)(ctx->scal + q.htab);
-            sp.vtab = (const int *)(ctx->scal + q.vtab);
+            sp.htab = (const int *)(sc.p + q.htab);
+            sp.vtab = (const int *)(sc.p + q.vtab);
             sp.th = q.th, sp.tv = q.tv;
-            sp.mid = (uint16_t *)(ctx->scal + tab_bytes + q.mid);
+            sp.mid = (uint16_t *)(sc.p + tab_bytes + q.mid);
             sp.mstride = q.mstride;
-            // ob consecutive outputs reach at most (ob - 1) pcw / ow + 2 max(pcw / ow, 1) + 1 source
-            // columns (either phase), and the tile spends up to 15 more on its 8-column runs
-            const int64_t room = (int64_t)(mi::kScaledSeg - 20) * q.ow - 2 * (int64_t)std::max(q.pcw, q.ow);
-            sp.ob = (int)std::min<int64_t>(room / q.pcw + 1, 1024);
+            sp.ob = mi::seg_outputs(q.pcw, q.ow);
             sp.segs = (q.ow + sp.ob - 1) / sp.ob;
             sp.xblocks = (q.ow + 1023) / 1024;
             sp.dst = (uint8_t *)o.data[p];
@@ -388,6 +280,6 @@ extern "C" int mi_display_scaled(MiCtx *ctx, const MiPicture *in, const MiScaled
         }
         if (mi::launch_scaled(a, in->bpc, o.bpc, (hipStream_t)stream)) return ctx->last_error = -EIO;
     }
-    memcpy(ctx->scal_key, key, sizeof(key));
+    sc.keep(tl);
     return 0;
 }

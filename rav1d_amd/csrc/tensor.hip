@@ -1,13 +1,12 @@
 // tensor.hip — mi_display_tensor (include/mi_av1out.h): a shown picture as the cropped, resized,
 // normalised R'G'B' tensor an ML consumer on the device reads, in one pass over the decoded planes.
 // The picture is the one MI_OUT_RGB_PLANAR gives (display.h: the same loads, chroma upsampler and
-// matrix); the resize is a separable triangle filter in 18-bit integers, horizontal pass first.
+// matrix); the resize is the separable 18-bit triangle filter of resize.h, both axes centred,
+// horizontal pass first.
 //
 // Three launches on the caller's stream, all scratch in one context-owned allocation:
-//   tensor_taps_kernel   one lane per output column / row: first tap, tap count and taps of the
-//                        header's integer formula, so the tables are ordered on the stream and no
-//                        host buffer is involved; skipped when the context's scratch still holds
-//                        the tables of the same two axes (the call before had this geometry);
+//   taps_kernel          (resize.h) the tap tables of the two axes; skipped when the context's
+//                        scratch still holds them (the call before had this geometry);
 //   tensor_h_kernel      one workgroup per (row unit, segment of output columns). A row unit is a
 //                        luma row, or for 4:2:0 the row pair sharing a chroma row, as in
 //                        display_kernel. A lane converts 8 source columns of the unit to R'G'B'
@@ -20,8 +19,6 @@
 //                        8-byte load of `mid` per channel (coalesced along x) and a wave-uniform
 //                        weight, the sums in registers; then finish and store in the
 //                        destination's order, as whole vectors where the pointer and strides allow.
-// Both passes run every slot of the tap table (zero weights past an output's own taps): with one
-// trip count the loops unroll and the loads of several taps are in flight together.
 //
 // mi_display_tensor_tm: the colour-volume stage (display.h tone_run) runs in the tile fill of
 // tensor_h_kernel, a compile-time switch, so the passes resize the tone-mapped picture at dst_bpc.
@@ -32,58 +29,10 @@
 
 #include <hip/hip_fp16.h>
 
-#include "display.h"
+#include "resize.h"
 
 namespace mi {
 namespace {
-
-// ---- taps ----
-// Output o of an axis n_in -> n_out: Rr = 2 max(n_in, n_out), C = (2o+1) n_in,
-// wt_i = Rr - |C - (2i+1) n_out| over every integer i, taps where wt_i > 0.
-__device__ __forceinline__ int64_t tap_wt(int64_t rr, int64_t c, int64_t n_out, int64_t i) {
-    const int64_t d = c - (2 * i + 1) * n_out;
-    return rr - (d < 0 ? -d : d);
-}
-
-__device__ void axis_taps(int n_in, int n_out, int o, int cap, int *start, int *count, int *k) {
-    const int64_t rr = 2 * (int64_t)max(n_in, n_out), c = (2 * (int64_t)o + 1) * n_in, n2 = 2 * (int64_t)n_out;
-    // floor((C - Rr) / 2 n_out) - 1 is left of the support: (2i+1) n_out <= C - Rr - n_out
-    const int64_t a = c - rr;
-    int64_t i0 = (a >= 0 ? a / n2 : -((-a + n2 - 1) / n2)) - 1;
-    while (tap_wt(rr, c, n_out, i0) <= 0) i0++;
-    int n = 0, best = 0;
-    int64_t wsum = 0, wbest = 0;
-    while (n < cap) {
-        const int64_t w = tap_wt(rr, c, n_out, i0 + n);
-        if (w <= 0) break;
-        wsum += w;
-        if (w > wbest) {   // the first tap with the largest weight
-            wbest = w;
-            best = n;
-        }
-        n++;
-    }
-    int64_t ksum = 0;
-    for (int j = 0; j < n; j++) {
-        const int64_t kj = ((tap_wt(rr, c, n_out, i0 + j) << kTensorS) + wsum / 2) / wsum;
-        k[(int64_t)j * n_out + o] = (int)kj;
-        ksum += kj;
-    }
-    k[(int64_t)best * n_out + o] += (int)(((int64_t)1 << kTensorS) - ksum);
-    // (the passes run all `cap` slots, so that their loops have one trip count and unroll)
-    for (int j = n; j < cap; j++) k[(int64_t)j * n_out + o] = 0;
-    start[o] = (int)i0;
-    count[o] = n;
-}
-
-__global__ __launch_bounds__(256) void tensor_taps_kernel(const TensorArgs t) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    int *hs = t.tab, *vs = t.tab + (int64_t)(t.th + 2) * t.ow;
-    if (i < t.ow)
-        axis_taps(t.cw, t.ow, i, t.th, hs, hs + t.ow, hs + 2 * t.ow);
-    else if (i - t.ow < t.oh)
-        axis_taps(t.ch, t.oh, i - t.ow, t.tv, vs, vs + t.oh, vs + 2 * t.oh);
-}
 
 // 8 pixels of one row to R'G'B' (with TM: through the colour-volume stage, to samples of dst_bpc),
 // one 16-byte LDS write per channel at column `col` of the tile
@@ -93,12 +42,9 @@ __device__ __forceinline__ void tile_row(const DisplayArgs &a, const ToneParam<T
     int R[8], G[8], B[8];
     convert_run(a, y, cu, cv, R, G, B);
     if constexpr (TM) tone_run(tm, lin, R, G, B);
-    *reinterpret_cast<uint4 *>(&tile[0][col]) = make_uint4((uint32_t)R[0] | ((uint32_t)R[1] << 16), (uint32_t)R[2] | ((uint32_t)R[3] << 16),
-                                                           (uint32_t)R[4] | ((uint32_t)R[5] << 16), (uint32_t)R[6] | ((uint32_t)R[7] << 16));
-    *reinterpret_cast<uint4 *>(&tile[1][col]) = make_uint4((uint32_t)G[0] | ((uint32_t)G[1] << 16), (uint32_t)G[2] | ((uint32_t)G[3] << 16),
-                                                           (uint32_t)G[4] | ((uint32_t)G[5] << 16), (uint32_t)G[6] | ((uint32_t)G[7] << 16));
-    *reinterpret_cast<uint4 *>(&tile[2][col]) = make_uint4((uint32_t)B[0] | ((uint32_t)B[1] << 16), (uint32_t)B[2] | ((uint32_t)B[3] << 16),
-                                                           (uint32_t)B[4] | ((uint32_t)B[5] << 16), (uint32_t)B[6] | ((uint32_t)B[7] << 16));
+    *reinterpret_cast<uint4 *>(&tile[0][col]) = pack8(R);
+    *reinterpret_cast<uint4 *>(&tile[1][col]) = pack8(G);
+    *reinterpret_cast<uint4 *>(&tile[2][col]) = pack8(B);
 }
 
 // ---- horizontal pass ----
@@ -133,25 +79,16 @@ __global__ __launch_bounds__(256) void tensor_h_kernel(const TensorArgs t, const
         if (rows & 2) tile_row<TM>(a, tm, lin, y[1], cu[1], cv[1], tile[1], x0 - xa);
     }
     __syncthreads();
-    // a lane owns (row, output column) items: per tap one weight (coalesced along o) and the
-    // three channels' samples; slots past an output's tap count hold zero weights
+    // a lane owns (row, output column) items and filters the three channels' samples
     const int nout = o1 - o0 + 1;
     for (int it = threadIdx.x; it < nout * 2; it += 256) {
         const int r = it >= nout, o = o0 + it - r * nout;
         if (!((rows >> r) & 1)) continue;
-        const int base = hs[o] + t.cx - xa, lo_i = t.cx - xa, hi_i = t.cx - xa + t.cw - 1;
+        const int base = hs[o] + t.cx - xa, lo_i = t.cx - xa, hi_i = min(t.cx - xa + t.cw - 1, kTensorSeg - 1);
         const int *k = hk + o;
-        int acc[3] = {1 << (kTensorS - 1), 1 << (kTensorS - 1), 1 << (kTensorS - 1)};
+        int acc[3] = {kTensorHalf, kTensorHalf, kTensorHalf};
 #pragma unroll 4
-        for (int j = 0; j < t.th; j++) {
-            // crop column clamp(s + j, 0, cw - 1) as a tile column; (the last min binds only for
-            // zero-weight slots: the host sizes ob so that an output's taps lie inside the tile)
-            const int idx = min(min(max(base + j, lo_i), hi_i), kTensorSeg - 1);
-            const int kj = k[(int64_t)j * t.ow];
-            acc[0] += kj * (int)tile[r][0][idx];
-            acc[1] += kj * (int)tile[r][1][idx];
-            acc[2] += kj * (int)tile[r][2][idx];
-        }
+        for (int j = 0; j < t.th; j++) h_tap<3>(tile[r], base + j, lo_i, hi_i, k[(int64_t)j * t.ow], acc);
         uint16_t *m = t.mid + (int64_t)(r0 + r - t.cy) * t.mstride + o;
 #pragma unroll
         for (int c = 0; c < 3; c++) m[(int64_t)c * t.ch * t.mstride] = (uint16_t)(acc[c] >> kTensorS);
@@ -207,29 +144,18 @@ __global__ __launch_bounds__(256) void tensor_v_kernel(const TensorArgs t) {
     const int x0 = (xb * 256 + (int)threadIdx.x) * 4;
     if (x0 >= t.ow) return;
     const int *vs = t.tab + (int64_t)(t.th + 2) * t.ow, *vk = vs + 2 * t.oh;
-    const int s = vs[oy];
     // (rows of mid are 16-byte aligned and x0 is a multiple of 4; columns past ow are padding)
+    const int s = vs[oy];
     const uint16_t *m = t.mid + x0;
     const int64_t plane = (int64_t)t.ch * t.mstride;
     int acc[3][4];
 #pragma unroll
     for (int c = 0; c < 3; c++)
 #pragma unroll
-        for (int i = 0; i < 4; i++) acc[c][i] = 1 << (kTensorS - 1);
-    // all tv slots (zero weights past the row's tap count): one trip count, so the loads of
-    // several taps are in flight together
+        for (int i = 0; i < 4; i++) acc[c][i] = kTensorHalf;
 #pragma unroll 4
-    for (int j = 0; j < t.tv; j++) {
-        const int row = min(max(s + j, 0), t.ch - 1), k = vk[(int64_t)j * t.oh + oy];
-#pragma unroll
-        for (int c = 0; c < 3; c++) {
-            const uint2 q = *reinterpret_cast<const uint2 *>(m + c * plane + row * t.mstride);
-            acc[c][0] += k * (int)(q.x & 0xffff);
-            acc[c][1] += k * (int)(q.x >> 16);
-            acc[c][2] += k * (int)(q.y & 0xffff);
-            acc[c][3] += k * (int)(q.y >> 16);
-        }
-    }
+    for (int j = 0; j < t.tv; j++)
+        v_tap<3>(m, plane, min(max(s + j, 0), t.ch - 1) * t.mstride, vk[(int64_t)j * t.oh + oy], acc);
     E e[3][4];
 #pragma unroll
     for (int c = 0; c < 3; c++)
@@ -287,11 +213,7 @@ void launch_v(const TensorArgs &t, int order, dim3 grid, hipStream_t s) {
 
 }  // namespace
 
-int launch_tensor(const TensorArgs &t, int bpc, int order, bool taps, hipStream_t s, const ToneArgs *tm) {
-    if (taps) {
-        tensor_taps_kernel<<<(t.ow + t.oh + 255) / 256, 256, 0, s>>>(t);
-        if (hipGetLastError() != hipSuccess) return -1;
-    }
+int launch_tensor(const TensorArgs &t, int bpc, int order, hipStream_t s, const ToneArgs *tm) {
     const dim3 hgrid(t.units, t.segs);
     if (tm) {
         if (bpc == 8)
@@ -321,14 +243,10 @@ namespace {
 // mi_display_tensor (tone false; tm not read) and mi_display_tensor_tm (tone true)
 int display_tensor(MiCtx *ctx, const MiPicture *in, const MiTensorImage *out, const MiColorInfo *color, bool tone,
                    const MiToneMap *tm, const MiFilmGrainData *fg, void *stream) {
-    if (!in || !out || !in->data[0] || in->w <= 0 || in->h <= 0 || in->w > 65536 || in->h > 65536 ||
-        in->layout < 0 || in->layout > 3 || (in->bpc != 8 && in->bpc != 10 && in->bpc != 12) || in->stride[0] <= 0)
-        return -EINVAL;
-    if (in->layout && (!in->data[1] || !in->data[2] || in->stride[1] <= 0)) return -EINVAL;
-    const int pxb = in->bpc == 8 ? 1 : 2, ss_hor = in->layout == 1 || in->layout == 2, ss_ver = in->layout == 1;
-    if ((int64_t)in->stride[0] < (int64_t)in->w * pxb ||
-        (in->layout && (int64_t)in->stride[1] < (int64_t)((in->w + ss_hor) >> ss_hor) * pxb))
-        return -EINVAL;
+    if (!in || !out) return -EINVAL;
+    if (int e = mi::display_check_picture(in)) return e;
+    if (int e = mi::display_check_strides(in)) return e;
+    const int ss_ver = in->layout == 1;
     // destination
     if (!out->data || out->w < 1 || out->h < 1 || out->w > 65536 || out->h > 65536) return -EINVAL;
     if (out->dtype != MI_T_U8 && out->dtype != MI_T_F16 && out->dtype != MI_T_BF16 && out->dtype != MI_T_F32)
@@ -337,12 +255,8 @@ int display_tensor(MiCtx *ctx, const MiPicture *in, const MiTensorImage *out, co
     for (int i = 0; i < 3; i++)
         if (out->stride[i] <= 0 || out->stride[i] % es) return -EINVAL;
     if ((uintptr_t)out->data % (uintptr_t)es) return -EINVAL;
-    // crop
-    int cx = 0, cy = 0, cw = in->w, ch = in->h;
-    if (out->crop_w || out->crop_h) {
-        cx = out->crop_x, cy = out->crop_y, cw = out->crop_w, ch = out->crop_h;
-        if (cx < 0 || cy < 0 || cw < 1 || ch < 1 || (int64_t)cx + cw > in->w || (int64_t)cy + ch > in->h) return -EINVAL;
-    }
+    int cx, cy, cw, ch;
+    if (int e = mi::display_crop(in, out->crop_x, out->crop_y, out->crop_w, out->crop_h, cx, cy, cw, ch)) return e;
     if ((int64_t)cw > 64 * (int64_t)out->w || (int64_t)ch > 64 * (int64_t)out->h) return -EINVAL;
     if (out->dtype != MI_T_U8)
         for (int c = 0; c < 3; c++)
@@ -358,13 +272,10 @@ int display_tensor(MiCtx *ctx, const MiPicture *in, const MiTensorImage *out, co
     // geometry of the passes and of the scratch
     const int ow = out->w, oh = out->h;
     t.cx = cx, t.cy = cy, t.cw = cw, t.ch = ch, t.ow = ow, t.oh = oh;
-    t.th = 2 * ((std::max(cw, ow) + ow - 1) / ow) + 1;
-    t.tv = 2 * ((std::max(ch, oh) + oh - 1) / oh) + 1;
+    t.th = mi::tap_cap(cw, ow);
+    t.tv = mi::tap_cap(ch, oh);
     t.mstride = ((int64_t)ow + 7) & ~(int64_t)7;
-    // ob consecutive outputs reach at most (ob - 1) cw / ow + 2 max(cw / ow, 1) + 1 source columns,
-    // and the tile spends up to 15 more on its 8-column runs
-    const int64_t room = (int64_t)(mi::kTensorSeg - 20) * ow - 2 * (int64_t)std::max(cw, ow);
-    t.ob = (int)std::min<int64_t>(room / cw + 1, 1024);
+    t.ob = mi::seg_outputs(cw, ow);
     t.segs = (ow + t.ob - 1) / t.ob;
     t.u0 = cy >> ss_ver;
     t.units = ((cy + ch - 1) >> ss_ver) - t.u0 + 1;
@@ -373,31 +284,23 @@ int display_tensor(MiCtx *ctx, const MiPicture *in, const MiTensorImage *out, co
     const size_t mid_bytes = (size_t)3 * ch * t.mstride * sizeof(uint16_t);
 
     // allocations first: a call that fails has launched nothing
-    if (tab_bytes + mid_bytes > ctx->tens_bytes) {
-        if (ctx->tens) (void)hipFree(ctx->tens);   // (waits for the work that reads it)
-        ctx->tens = nullptr;
-        ctx->tens_bytes = 0;
-        memset(ctx->tens_geom, 0, sizeof(ctx->tens_geom));
-        if (hipMalloc(&ctx->tens, tab_bytes + mid_bytes) != hipSuccess) return ctx->last_error = -ENOMEM;
-        ctx->tens_bytes = tab_bytes + mid_bytes;
-    }
-    // The tap tables depend on the two axes' extents alone and stay in the scratch: a call with
-    // the geometry of the one before it on this context (every picture of a stream, as a rule)
-    // reuses them, ordered behind their launch on the context's stream.
-    const int geom[4] = {cw, ow, ch, oh};
-    const bool taps = memcmp(geom, ctx->tens_geom, sizeof(geom)) != 0;
+    MiResizeScratch &sc = ctx->tens;
+    if (!sc.ensure(tab_bytes + mid_bytes)) return ctx->last_error = -ENOMEM;
+    t.tab = (int *)sc.p;
+    t.mid = (uint16_t *)(sc.p + tab_bytes);
+    mi::TapList tl;
+    memset(&tl, 0, sizeof(tl));
+    tl.ax[tl.n++] = mi::TapAxis{cw, ow, 2, t.th, t.tab};
+    tl.ax[tl.n++] = mi::TapAxis{ch, oh, 2, t.tv, t.tab + (int64_t)(t.th + 2) * ow};
+    const bool taps = !sc.holds(tl);
     mi::ToneArgs ta;
     if (tone)
         if (int e = mi::tone_prepare(ctx, tm, color, in->bpc, (hipStream_t)stream, ta)) return e;
     MiPicture src = *in;
-    if (fg) {
-        if (int e = mi::display_grain_picture(ctx, in, &src)) return e;
-        if (int e = mi_film_grain_frame(ctx, in, &src, fg, color->mtrx == 0, stream)) return e;
-    }
+    if (fg)
+        if (int e = mi::display_grain(ctx, in, &src, fg, color, stream)) return e;
 
     mi::display_source(src, color, t.d);
-    t.tab = (int *)ctx->tens;
-    t.mid = (uint16_t *)(ctx->tens + tab_bytes);
     t.dst = (uint8_t *)out->data;
     for (int i = 0; i < 3; i++) t.dstride[i] = out->stride[i];
     t.dtype = out->dtype;
@@ -413,9 +316,11 @@ int display_tensor(MiCtx *ctx, const MiPicture *in, const MiTensorImage *out, co
         order = mi::kTensorHWC;
         t.vec = !(((uintptr_t)out->data | (uintptr_t)out->stride[1]) & v4);
     }
-    memset(ctx->tens_geom, 0, sizeof(ctx->tens_geom));
-    if (mi::launch_tensor(t, in->bpc, order, taps, (hipStream_t)stream, tone ? &ta : nullptr)) return ctx->last_error = -EIO;
-    memcpy(ctx->tens_geom, geom, sizeof(geom));
+    sc.forget();
+    if ((taps && mi::launch_taps(tl, (hipStream_t)stream)) ||
+        mi::launch_tensor(t, in->bpc, order, (hipStream_t)stream, tone ? &ta : nullptr))
+        return ctx->last_error = -EIO;
+    sc.keep(tl);
     return 0;
 }
 

@@ -292,6 +292,33 @@ def test_scratch_and_tap_table_reuse(gpu):
     ctx.close()
 
 
+def test_tensor_and_scaled_share_luma_axes(gpu):
+    """The two outputs fill their tap tables with one kernel and key them by the axis list. One
+    context of its own, a 4:2:0 source with chr 2, mi_display_tensor and mi_display_scaled to the
+    same 24 x 10 in turn, three times round: the luma axes of the two are identical (66 -> 24 and
+    34 -> 10, centred) and only the scaled output's co-sited chroma axes differ, the smallest case
+    in which tables or keys taken for one another would show. Each result equals its model."""
+    from rav1d_amd.frame import Context
+    ctx = Context(0)
+    w, h, bpc, layout, chr, size = 66, 34, 8, 1, 2, (24, 10)
+    planes = make_planes(np.random.default_rng(11), w, h, bpc, layout, "random")
+    src = to_frame(planes, w, h, bpc, layout)
+    want_t = T.tensor(planes, bpc, layout, (1, 0, chr), None, size, T.U8)
+    want_s = Z.scaled(planes, bpc, layout, chr, size)
+    jobs = []
+    for _ in range(3):
+        out = torch.zeros((3, size[1], size[0]), dtype=torch.uint8, device="cuda")
+        display_tensor(ctx, src, out, MiColorInfo(1, 1, 1, 0, chr))
+        d = Dest(size[0], size[1], bpc, layout)
+        assert call(ctx, src, [d], chr) == 0
+        jobs.append((out, d))
+    torch.cuda.synchronize()
+    for i, (out, d) in enumerate(jobs):
+        assert np.array_equal(out.cpu().numpy(), want_t), i
+        same(d.planes(), want_s, (i,))
+    ctx.close()
+
+
 def test_scaled_image_tensors(gpu):
     """ScaledImage allocates the tensors; display_scaled fills one image or a list of them."""
     w, h, bpc, layout = 17, 9, 10, 1
