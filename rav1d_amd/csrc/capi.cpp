@@ -1,9 +1,7 @@
-// capi.cpp — the C-ABI of include/mi_av1dsp.h: contexts, the batched per-frame entry points
-// and the table-compatible per-call entry points.
-//
-// The per-call entry points keep the reference's contract (caller owns buffers, callee zeroes
-// the consumed coefficients, src/itx.rs:152-158) and accept host or device pointers; they run
-// a one-block launch synchronously on a private stream of device 0.
+// capi.cpp — the C-ABI of include/mi_av1dsp.h: contexts and the batched per-frame entry points
+// (mi_itx_frame*, mi_mc_*, mi_ipred_blocks / mi_intra_*, mi_deblock_*, mi_cdef_*, mi_lr_*,
+// mi_film_grain_*), and mi_internal::intra_recon. The table-compatible per-call entry points
+// (mi_dsp_*) are in dsp_calls.cpp.
 #include <stdio.h>
 #include <stdlib.h>
 #include <algorithm>
@@ -22,50 +20,6 @@ int fail(MiCtx *c, int e) {
     if (c) c->last_error = e;
     return e;
 }
-
-bool is_device_ptr(const void *p) {
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    return at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged;
-}
-
-// Private state for the synchronous per-call entry points.
-struct CallState {
-    std::mutex mu;
-    bool ready = false;
-    int err = 0;
-    hipStream_t stream = nullptr;
-    uint8_t *scratch = nullptr;     // pixels / coefficients / descriptors
-    size_t scratch_bytes = 0;
-    int init() {
-        if (ready) return err;
-        ready = true;
-        int n = 0;
-        if (hipGetDeviceCount(&n) != hipSuccess || n == 0) return err = -ENODEV;
-        if (hipSetDevice(0) != hipSuccess) return err = -ENODEV;
-        if (hipStreamCreateWithFlags(&stream, hipStreamNonBlocking) != hipSuccess) return err = -EIO;
-        scratch_bytes = 1 << 20;
-        if (hipMalloc(&scratch, scratch_bytes) != hipSuccess) return err = -ENOMEM;
-        return err = 0;
-    }
-    int reserve(size_t n) {   // grow the scratch (only ever grows; callers hold mu)
-        if (n <= scratch_bytes) return 0;
-        if (hipStreamSynchronize(stream) != hipSuccess) return -EIO;
-        (void)hipFree(scratch);
-        scratch = nullptr;
-        scratch_bytes = 0;
-        if (hipMalloc(&scratch, n) != hipSuccess) {
-            if (hipMalloc(&scratch, 1 << 20) == hipSuccess) scratch_bytes = 1 << 20;
-            return -ENOMEM;
-        }
-        scratch_bytes = n;
-        return 0;
-    }
-};
-CallState g_call;
 
 // The context's device words ([0..63] queue heads, [64] dependency-wait give-up / untaken
 // blocks, [65] rejected descriptors, [72..79] XCD worker ranks), allocated zeroed on first use.
@@ -272,6 +226,22 @@ int fill_mc_args(mi::McArgs &a, const MiPicture *cur, const MiPicture *refs, int
     return 0;
 }
 }  // namespace
+
+namespace mi_internal {
+int fg_tables() {
+    static std::once_flag once;
+    static int tables_rc = 0;
+    std::call_once(once, [] { tables_rc = mi::init_fg_tables(); });
+    return tables_rc ? -EIO : 0;
+}
+bool fg_data_ok(const MiFilmGrainData *data) {
+    return !(data->num_y_points < 0 || data->num_y_points > 14 || data->ar_coeff_lag < 0 || data->ar_coeff_lag > 3 ||
+             data->num_uv_points[0] < 0 || data->num_uv_points[0] > 10 || data->num_uv_points[1] < 0 ||
+             data->num_uv_points[1] > 10 || data->ar_coeff_shift < 6 || data->ar_coeff_shift > 9);
+}
+}  // namespace mi_internal
+using mi_internal::fg_data_ok;
+using mi_internal::fg_tables;
 
 extern "C" {
 
@@ -862,18 +832,6 @@ int mi_lr_tile_order(const MiAv1Restoration *mask, int w, int h, int layout, con
     return a.blk_start[3];
 }
 
-static int fg_tables() {
-    static std::once_flag once;
-    static int tables_rc = 0;
-    std::call_once(once, [] { tables_rc = mi::init_fg_tables(); });
-    return tables_rc ? -EIO : 0;
-}
-static bool fg_data_ok(const MiFilmGrainData *data) {
-    return !(data->num_y_points < 0 || data->num_y_points > 14 || data->ar_coeff_lag < 0 || data->ar_coeff_lag > 3 ||
-             data->num_uv_points[0] < 0 || data->num_uv_points[0] > 10 || data->num_uv_points[1] < 0 ||
-             data->num_uv_points[1] > 10 || data->ar_coeff_shift < 6 || data->ar_coeff_shift > 9);
-}
-
 static int fg_setup(MiCtx *ctx, const MiPicture *in, const MiPicture *out, const MiFilmGrainData *data,
                     int is_id, mi::FgArgs &a) {
     if (int e = fg_tables()) return e;
@@ -947,887 +905,7 @@ int mi_film_grain_frame(MiCtx *ctx, const MiPicture *in, const MiPicture *out, c
     if (int e = fg_setup(ctx, in, out, data, mtrx_identity, a)) return fail(ctx, e);
     return mi::launch_fg(a, (hipStream_t)stream, true, true) ? fail(ctx, -EIO) : 0;
 }
-
-// ---- table-compatible per-call entry points ------------------------------------------
-
-int mi_dsp_itxfm_add(int tx, int txtp, void *dst, ptrdiff_t stride, void *coeff, int eob,
-                     int bitdepth_max) {
-    if (tx < 0 || tx >= MI_N_RECT_TX_SIZES || !mi::itx_type_valid(tx, txtp) || !dst || !coeff ||
-        eob < 0)
-        return -EINVAL;
-    const int bpc = bitdepth_max == 255 ? 8 : bitdepth_max == 1023 ? 10 : bitdepth_max == 4095 ? 12 : 0;
-    if (!bpc) return -EINVAL;
-    std::lock_guard<std::mutex> lk(g_call.mu);
-    if (int e = g_call.init()) return e;
-    if (hipSetDevice(0) != hipSuccess) return -ENODEV;
-
-    const mi::TxDim d = mi::tx_dim(tx);
-    const int px = bpc == 8 ? 1 : 2, cb = bpc == 8 ? 2 : 4;
-    const size_t ncoef = (size_t)mi::imin_c(d.w, 32) * mi::imin_c(d.h, 32);
-    const size_t row_bytes = (size_t)d.w * px;
-    hipStream_t s = g_call.stream;
-
-    // device layout in scratch: [pixels h*row_bytes][coef][descriptor]
-    uint8_t *dpix = g_call.scratch;
-    uint8_t *dcoef = dpix + 64 * 128;
-    MiTxBlock *dblk = (MiTxBlock *)(dcoef + 32 * 32 * 4);
-
-    const bool dst_dev = is_device_ptr(dst), cf_dev = is_device_ptr(coeff);
-    std::vector<uint8_t> hpix;
-    if (dst_dev) {
-        for (int y = 0; y < d.h; y++)
-            if (hipMemcpyAsync(dpix + y * row_bytes, (uint8_t *)dst + y * stride, row_bytes, hipMemcpyDeviceToDevice, s) != hipSuccess)
-                return -EIO;
-    } else {
-        hpix.resize(row_bytes * d.h);
-        for (int y = 0; y < d.h; y++) memcpy(&hpix[y * row_bytes], (uint8_t *)dst + y * stride, row_bytes);
-        if (hipMemcpyAsync(dpix, hpix.data(), hpix.size(), hipMemcpyHostToDevice, s) != hipSuccess) return -EIO;
-    }
-    if (hipMemcpyAsync(dcoef, coeff, ncoef * cb, cf_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s) != hipSuccess)
-        return -EIO;
-    MiTxBlock hb{};
-    hb.tx = (uint8_t)tx;
-    hb.txtp = (uint8_t)txtp;
-    hb.eob = eob;
-    if (hipMemcpyAsync(dblk, &hb, sizeof(hb), hipMemcpyHostToDevice, s) != hipSuccess) return -EIO;
-
-    mi::ItxArgs a;
-    memset(&a, 0, sizeof(a));
-    for (int p = 0; p < 3; p++) { a.plane[p] = dpix; a.stride[p] = (int64_t)row_bytes; }
-    a.blocks = dblk;
-    a.coef = dcoef;
-    a.bdmax = bitdepth_max;
-    a.zero_coefs = 1;
-    a.pw[0] = d.w;
-    a.ph[0] = d.h;
-    a.err = (int *)(dblk + 1);   // scratch word: the host checked tx / txtp above
-    uint32_t ss1[MI_N_RECT_TX_SIZES + 1];
-    for (int k = 0; k <= MI_N_RECT_TX_SIZES; k++) ss1[k] = k > tx ? 1 : 0;
-    const int nwg = mi::itx_fill_schedule(a, ss1);
-    if (mi::launch_itx_frame(a, nwg, bpc, s)) return -EIO;
-
-    if (dst_dev) {
-        for (int y = 0; y < d.h; y++)
-            if (hipMemcpyAsync((uint8_t *)dst + y * stride, dpix + y * row_bytes, row_bytes, hipMemcpyDeviceToDevice, s) != hipSuccess)
-                return -EIO;
-    } else {
-        if (hipMemcpyAsync(hpix.data(), dpix, hpix.size(), hipMemcpyDeviceToHost, s) != hipSuccess) return -EIO;
-    }
-    if (hipMemcpyAsync(coeff, dcoef, ncoef * cb, cf_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s) != hipSuccess)
-        return -EIO;
-    if (hipStreamSynchronize(s) != hipSuccess) return -EIO;
-    if (!dst_dev)
-        for (int y = 0; y < d.h; y++) memcpy((uint8_t *)dst + y * stride, &hpix[y * row_bytes], row_bytes);
-    return 0;
-}
-
-int mi_dsp_intra_pred(int mode, void *dst, ptrdiff_t stride, const void *topleft, int w, int h,
-                      int angle, int max_width, int max_height, int bitdepth_max) {
-    if (mode < 0 || mode > 13 || !dst || !topleft || w < 4 || h < 4 || w > 64 || h > 64 ||
-        (w & (w - 1)) || (h & (h - 1)) || (mode == 13 && (w > 32 || h > 32)))
-        return -EINVAL;
-    const int bpc = bitdepth_max == 255 ? 8 : bitdepth_max == 1023 ? 10 : bitdepth_max == 4095 ? 12 : 0;
-    if (!bpc) return -EINVAL;
-    std::lock_guard<std::mutex> lk(g_call.mu);
-    if (int e = g_call.init()) return e;
-    if (hipSetDevice(0) != hipSuccess) return -ENODEV;
-    const int px = bpc == 8 ? 1 : 2;
-    const size_t row_bytes = (size_t)w * px;
-    hipStream_t s = g_call.stream;
-    // device scratch: [pixels 64 rows x 128 B][edge 257 samples][descriptor]
-    uint8_t *dpix = g_call.scratch;
-    uint8_t *dedge = dpix + 64 * 128;
-    MiIpredBlock *dblk = (MiIpredBlock *)(dedge + 1024);
-    const int ext = w + h;                      // samples read on each side of topleft
-    const uint8_t *esrc = (const uint8_t *)topleft - (ptrdiff_t)ext * px;
-    const hipMemcpyKind ek = is_device_ptr(topleft) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-    if (hipMemcpyAsync(dedge, esrc, (size_t)(2 * ext + 1) * px, ek, s) != hipSuccess) return -EIO;
-    MiIpredBlock hb{};
-    hb.edge_off = (uint32_t)ext;
-    hb.w = (uint8_t)w;
-    hb.h = (uint8_t)h;
-    hb.mode = (uint8_t)mode;
-    hb.angle = (uint16_t)angle;
-    hb.max_w = (uint16_t)max_width;
-    hb.max_h = (uint16_t)max_height;
-    if (hipMemcpyAsync(dblk, &hb, sizeof(hb), hipMemcpyHostToDevice, s) != hipSuccess) return -EIO;
-    mi::IpredArgs a;
-    memset(&a, 0, sizeof(a));
-    for (int p = 0; p < 3; p++) a.dst[p] = dpix;
-    a.stride[0] = a.stride[1] = (int64_t)row_bytes;
-    a.blocks = dblk;
-    a.edges = dedge;
-    a.bpc = bpc;
-    a.bdmax = bitdepth_max;
-    if (mi::launch_ipred(a, 1, s)) return -EIO;
-    const bool dst_dev = is_device_ptr(dst);
-    std::vector<uint8_t> hpix(dst_dev ? 0 : row_bytes * h);
-    for (int y = 0; y < h; y++) {
-        const hipError_t e = dst_dev
-            ? hipMemcpyAsync((uint8_t *)dst + y * stride, dpix + y * row_bytes, row_bytes, hipMemcpyDeviceToDevice, s)
-            : hipMemcpyAsync(&hpix[y * row_bytes], dpix + y * row_bytes, row_bytes, hipMemcpyDeviceToHost, s);
-        if (e != hipSuccess) return -EIO;
-    }
-    if (hipStreamSynchronize(s) != hipSuccess) return -EIO;
-    if (!dst_dev)
-        for (int y = 0; y < h; y++) memcpy((uint8_t *)dst + y * stride, &hpix[y * row_bytes], row_bytes);
-    return 0;
-}
-
-// ---- helpers of the remaining per-call entries: caller pixel windows <-> device scratch ----
-namespace {
-int bpc_of(int bitdepth_max) {
-    return bitdepth_max == 255 ? 8 : bitdepth_max == 1023 ? 10 : bitdepth_max == 4095 ? 12 : 0;
-}
-// rows [r0, r1) x bytes [b0, b1) around `base` (host or device, any stride sign) <-> a packed
-// device window of pitch (b1 - b0)
-int win_in(uint8_t *dev, const void *base, ptrdiff_t stride, int r0, int r1, ptrdiff_t b0, ptrdiff_t b1, hipStream_t s) {
-    for (int r = r0; r < r1; r++)
-        if (hipMemcpyAsync(dev + (size_t)(r - r0) * (b1 - b0), (const uint8_t *)base + r * stride + b0, b1 - b0,
-                           hipMemcpyDefault, s) != hipSuccess)
-            return -EIO;
-    return 0;
-}
-int win_out(void *base, ptrdiff_t stride, const uint8_t *dev, int r0, int r1, ptrdiff_t b0, ptrdiff_t b1, hipStream_t s) {
-    for (int r = r0; r < r1; r++)
-        if (hipMemcpyAsync((uint8_t *)base + r * stride + b0, dev + (size_t)(r - r0) * (b1 - b0), b1 - b0,
-                           hipMemcpyDefault, s) != hipSuccess)
-            return -EIO;
-    return hipStreamSynchronize(s) == hipSuccess ? 0 : -EIO;
-}
-int copy_in(void *dev, const void *src, size_t n, hipStream_t s) {
-    return hipMemcpyAsync(dev, src, n, hipMemcpyDefault, s) == hipSuccess ? 0 : -EIO;
-}
-}  // namespace
-
-extern "C" {
-
-int mi_dsp_cfl_pred(int mode, void *dst, ptrdiff_t stride, const void *topleft, int w, int h, const int16_t *ac,
-                    int alpha, int bitdepth_max) {
-    const int bpc = bpc_of(bitdepth_max);
-    if (!bpc || !dst || !topleft || !ac || (mode != 0 && mode != 3 && mode != 4 && mode != 5) || w < 4 || h < 4 ||
-        w > 32 || h > 32 || (w & (w - 1)) || (h & (h - 1)))
-        return -EINVAL;
-    std::lock_guard<std::mutex> lk(g_call.mu);
-    if (int e = g_call.init()) return e;
-    const int px = bpc == 8 ? 1 : 2;
-    hipStream_t s = g_call.stream;
-    uint8_t *dpix = g_call.scratch, *dedge = dpix + 64 * 128, *dac = dedge + 1024;
-    MiIpredBlock *dblk = (MiIpredBlock *)(dac + 64 * 64 * 2);
-    int e = copy_in(dedge, (const uint8_t *)topleft - (ptrdiff_t)h * px, (size_t)(w + h + 1) * px, s);
-    if (!e) e = copy_in(dac, ac, (size_t)w * h * 2, s);
-    MiIpredBlock hb{};
-    hb.edge_off = (uint32_t)h;
-    hb.w = (uint8_t)w;
-    hb.h = (uint8_t)h;
-    hb.mode = (uint8_t)(MI_IPRED_CFL + mode);
-    hb.alpha = (int8_t)alpha;
-    if (!e) e = copy_in(dblk, &hb, sizeof(hb), s);
-    if (e) return e;
-    mi::IpredArgs a;
-    memset(&a, 0, sizeof(a));
-    for (int p = 0; p < 3; p++) a.dst[p] = dpix;
-    a.stride[0] = a.stride[1] = (int64_t)w * px;
-    a.blocks = dblk;
-    a.edges = dedge;
-    a.ac = (const int16_t *)dac;
-    a.bpc = bpc;
-    a.bdmax = bitdepth_max;
-    if (mi::launch_ipred(a, 1, s)) return -EIO;
-    return win_out(dst, stride, dpix, 0, h, 0, (ptrdiff_t)w * px, s);
-}
-
-int mi_dsp_pal_pred(void *dst, ptrdiff_t stride, const void *pal, const uint8_t *idx, int w, int h, int bitdepth_max) {
-    const int bpc = bpc_of(bitdepth_max);
-    if (!bpc || !dst || !pal || !idx || w < 4 || h < 4 || w > 64 || h > 64) return -EINVAL;
-    std::lock_guard<std::mutex> lk(g_call.mu);
-    if (int e = g_call.init()) return e;
-    const int px = bpc == 8 ? 1 : 2;
-    hipStream_t s = g_call.stream;
-    uint8_t *dpix = g_call.scratch, *dpal = dpix + 64 * 128, *didx = dpal + 64;
-    MiIpredBlock *dblk = (MiIpredBlock *)(didx + 64 * 64);
-    int e = copy_in(dpal, pal, 8 * (size_t)px, s);
-    if (!e) e = copy_in(didx, idx, (size_t)w * h, s);
-    MiIpredBlock hb{};
-    hb.w = (uint8_t)w;
-    hb.h = (uint8_t)h;
-    hb.mode = MI_IPRED_PAL;
-    if (!e) e = copy_in(dblk, &hb, sizeof(hb), s);
-    if (e) return e;
-    mi::IpredArgs a;
-    memset(&a, 0, sizeof(a));
-    for (int p = 0; p < 3; p++) a.dst[p] = dpix;
-    a.stride[0] = a.stride[1] = (int64_t)w * px;
-    a.blocks = dblk;
-    a.edges = dpal;
-    a.idx = didx;
-    a.bpc = bpc;
-    a.bdmax = bitdepth_max;
-    if (mi::launch_ipred(a, 1, s)) return -EIO;
-    return win_out(dst, stride, dpix, 0, h, 0, (ptrdiff_t)w * px, s);
-}
-
-int mi_dsp_cfl_ac(int layout, int16_t *ac, const void *y, ptrdiff_t stride, int w_pad, int h_pad, int cw, int ch,
-                  int bitdepth_max) {
-    const int bpc = bpc_of(bitdepth_max);
-    if (!bpc || !ac || !y || layout < 1 || layout > 3 || cw < 4 || ch < 4 || cw > 32 || ch > 32 ||
-        (cw & (cw - 1)) || (ch & (ch - 1)) || w_pad < 0 || h_pad < 0 || 4 * w_pad >= cw || 4 * h_pad >= ch)
-        return -EINVAL;
-    std::lock_guard<std::mutex> lk(g_call.mu);
-    if (int e = g_call.init()) return e;
-    const int px = bpc == 8 ? 1 : 2;
-    const int ss_hor = layout != 3, ss_ver = layout == 1;
-    const int rows = (ch - 4 * h_pad) << ss_ver, cols = (cw - 4 * w_pad) << ss_hor;
-    hipStream_t s = g_call.stream;
-    uint8_t *dy = g_call.scratch;
-    int16_t *dac = (int16_t *)(dy + 64 * 128);
-    if (int e = win_in(dy, y, stride, 0, rows, 0, (ptrdiff_t)cols * px, s)) return e;
-    mi::CflAcArgs a;
-    a.ac = dac;
-    a.y = dy;
-    a.stride = (int64_t)cols * px;
-    a.w_pad = w_pad;
-    a.h_pad = h_pad;
-    a.cw = cw;
-    a.ch = ch;
-    a.ss_hor = ss_hor;
-    a.ss_ver = ss_ver;
-    if (mi::launch_cfl_ac(a, bpc, s)) return -EIO;
-    if (hipMemcpyAsync(ac, dac, (size_t)cw * ch * 2, hipMemcpyDefault, s) != hipSuccess) return -EIO;
-    return hipStreamSynchronize(s) == hipSuccess ? 0 : -EIO;
-}
-
-int mi_dsp_loop_filter_sb(int cls, int dir, void *dst, ptrdiff_t stride, const uint32_t *vmask,
-                          const uint8_t (*lvl)[4], ptrdiff_t b4_stride, const void *lut, int wh, int bitdepth_max) {
-    (void)wh;
-    const int bpc = bpc_of(bitdepth_max);
-    if (!bpc || cls < 0 || cls > 1 || dir < 0 || dir > 1 || !dst || !vmask || !lvl || !lut) return -EINVAL;
-    std::lock_guard<std::mutex> lk(g_call.mu);
-    if (int e = g_call.init()) return e;
-    const int px = bpc == 8 ? 1 : 2;
-    hipStream_t s = g_call.stream;
-    mi::LfCallArgs a;
-    memset(&a, 0, sizeof(a));
-    if (hipMemcpy(a.vmask, vmask, (cls ? 2 : 3) * sizeof(uint32_t), hipMemcpyDefault) != hipSuccess) return -EIO;
-    const unsigned vm = a.vmask[0] | a.vmask[1] | a.vmask[2];
-    if (!vm) return 0;
-    const int nu = 32 - __builtin_clz(vm);                 // units up to the highest set bit
-    // level pairs {unit, neighbour}: the caller's map is strided (b4_stride entries per row)
-    uint8_t lv[64] = {0};
-    const ptrdiff_t ul = dir == 0 ? b4_stride : 1, pl = dir == 0 ? -1 : -b4_stride;
-    for (int k = 0; k < nu; k++) {
-        if (!(vm & (1u << k))) continue;
-        if (hipMemcpy(&lv[2 * k], &lvl[k * ul][0], 1, hipMemcpyDefault) != hipSuccess ||
-            hipMemcpy(&lv[2 * k + 1], &lvl[k * ul + pl][0], 1, hipMemcpyDefault) != hipSuccess)
-            return -EIO;
-    }
-    uint8_t lt[128];
-    if (hipMemcpy(lt, lut, 128, hipMemcpyDefault) != hipSuccess) return -EIO;   // Av1FilterLUT.e, .i
-    memcpy(a.lim_e, lt, 64);
-    memcpy(a.lim_i, lt + 64, 64);
-    // the pixel window: 8 samples either side of the edge, 4 * nu along it
-    const int r0 = dir == 0 ? 0 : -8, r1 = dir == 0 ? 4 * nu : 8;
-    const ptrdiff_t b0 = (dir == 0 ? -8 : 0) * px, b1 = (dir == 0 ? 8 : 4 * nu) * px;
-    uint8_t *dwin = g_call.scratch, *dlv = dwin + (1 << 19);
-    if (int e = win_in(dwin, dst, stride, r0, r1, b0, b1, s)) return e;
-    if (int e = copy_in(dlv, lv, sizeof(lv), s)) return e;
-    a.dst = dwin + (size_t)(-r0) * (b1 - b0) - b0;
-    a.stride = b1 - b0;
-    a.lvl = dlv;
-    a.cls = cls;
-    a.dir = dir;
-    a.bdm8 = bpc - 8;
-    a.bdmax = bitdepth_max;
-    if (mi::launch_lf_sb_call(a, bpc, s)) return -EIO;
-    return win_out(dst, stride, dwin, r0, r1, b0, b1, s);
-}
-
-int mi_dsp_cdef_filter(int fb, void *dst, ptrdiff_t stride, const void *left, const void *top, const void *bottom,
-                       int pri, int sec, int dir, int damping, int edges, int bitdepth_max) {
-    const int bpc = bpc_of(bitdepth_max);
-    if (!bpc || fb < 0 || fb > 2 || !dst || dir < 0 || dir > 7 || pri < 0 || sec < 0) return -EINVAL;
-    const int w = fb == 0 ? 8 : 4, h = fb == 2 ? 4 : 8;
-    if (((edges & 1) && !left) || ((edges & 4) && !top) || ((edges & 8) && !bottom)) return -EINVAL;
-    std::lock_guard<std::mutex> lk(g_call.mu);
-    if (int e = g_call.init()) return e;
-    const int px = bpc == 8 ? 1 : 2;
-    hipStream_t s = g_call.stream;
-    // one packed window, pitch P, column 0 = x - 2: rows 0-1 from top, 2..h+1 the block,
-    // h+2..h+3 from bottom; only the columns the edge flags allow are read from the caller
-    const ptrdiff_t P = (ptrdiff_t)(w + 4) * px;
-    const ptrdiff_t x0 = (edges & 1) ? -2 * px : 0, x1 = (ptrdiff_t)(w + ((edges & 2) ? 2 : 0)) * px;
-    uint8_t *win = g_call.scratch, *dleft = win + 4096, *dout = dleft + 4096;
-    auto rows = [&](const void *src, int r0, int n, ptrdiff_t c0) -> int {
-        for (int r = 0; r < n; r++)
-            if (hipMemcpyAsync(win + (size_t)(r0 + r) * P + 2 * px + c0, (const uint8_t *)src + r * stride + c0, x1 - c0,
-                               hipMemcpyDefault, s) != hipSuccess)
-                return -EIO;
-        return 0;
-    };
-    int e = rows(dst, 2, h, 0);
-    if (!e && (edges & 4)) e = rows(top, 0, 2, x0);
-    if (!e && (edges & 8)) e = rows(bottom, 2 + h, 2, x0);
-    if (!e && (edges & 1)) e = copy_in(dleft, left, (size_t)h * 2 * px, s);
-    if (e) return e;
-    mi::CdefCallArgs a;
-    memset(&a, 0, sizeof(a));
-    a.top = win + 2 * px;
-    a.dst = win + 2 * P + 2 * px;
-    a.bottom = win + (2 + h) * P + 2 * px;
-    a.left = dleft;
-    a.out = dout;
-    a.stride = P;
-    a.w = w;
-    a.h = h;
-    a.pri = pri;
-    a.sec = sec;
-    a.dir = dir;
-    a.damping = damping;
-    a.edges = edges;
-    a.bdm8 = bpc - 8;
-    if (mi::launch_cdef_call(a, bpc, false, s)) return -EIO;
-    return win_out(dst, stride, dout, 0, h, 0, (ptrdiff_t)w * px, s);
-}
-
-int mi_dsp_cdef_dir(const void *img, ptrdiff_t stride, unsigned *var, int bitdepth_max) {
-    const int bpc = bpc_of(bitdepth_max);
-    if (!bpc || !img || !var) return -EINVAL;
-    std::lock_guard<std::mutex> lk(g_call.mu);
-    if (int e = g_call.init()) return e;
-    const int px = bpc == 8 ? 1 : 2;
-    hipStream_t s = g_call.stream;
-    uint8_t *win = g_call.scratch, *dout = win + 4096;
-    if (int e = win_in(win, img, stride, 0, 8, 0, 8 * px, s)) return e;
-    mi::CdefCallArgs a;
-    memset(&a, 0, sizeof(a));
-    a.dst = win;
-    a.out = dout;
-    a.stride = 8 * px;
-    a.bdm8 = bpc - 8;
-    if (mi::launch_cdef_call(a, bpc, true, s)) return -EIO;
-    int r[2];
-    if (hipMemcpyAsync(r, dout, sizeof(r), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-        return -EIO;
-    *var = (unsigned)r[1];
-    return r[0];
-}
-
-// ---- mc table (src/mc.rs:1174-1338): put / prep, combine, blend, emu_edge ----
-namespace {
-void mc_call_bd(mi::McCallArgs &a, int bpc, int bdmax) {
-    a.bpc = bpc;
-    a.ib = bpc == 8 ? 4 : 14 - bpc;
-    a.bias = bpc == 8 ? 0 : 8192;
-    a.bdmax = bdmax;
-}
-bool mc_dims_ok(int w, int h) { return w >= 2 && h >= 2 && w <= 128 && h <= 128; }
-}  // namespace
-
-int mi_dsp_mc_put(int filter2d, void *dst, ptrdiff_t dst_stride, const void *src, ptrdiff_t src_stride, int w, int h,
-                  int mx, int my, int bitdepth_max) {
-    const int bpc = bpc_of(bitdepth_max);
-    if (!bpc || !dst || !src || filter2d < 0 || filter2d > 9 || !mc_dims_ok(w, h) || mx < 0 || mx > 15 || my < 0 ||
-        my > 15)
-        return -EINVAL;
-    std::lock_guard<std::mutex> lk(g_call.mu);
-    if (int e = g_call.init()) return e;
-    const int px = bpc == 8 ? 1 : 2;
-    hipStream_t s = g_call.stream;
-    // source window: rows -3 .. h+4, columns -3 .. w+4 (8-tap reach; bilinear uses +1)
-    const int r0 = filter2d == 9 ? 0 : -3, r1 = h + (filter2d == 9 ? 1 : 5);
-    const ptrdiff_t b0 = (filter2d == 9 ? 0 : -3) * px, b1 = (ptrdiff_t)(w + (filter2d == 9 ? 1 : 5)) * px;
-    uint8_t *win = g_call.scratch, *dout = win + (1 << 19);
-    if (int e = win_in(win, src, src_stride, r0, r1, b0, b1, s)) return e;
-    mi::McCallArgs a;
-    memset(&a, 0, sizeof(a));
-    a.src = win + (size_t)(-r0) * (b1 - b0) - b0;
-    a.src_stride = b1 - b0;
-    a.dst = dout;
-    a.dst_stride = (int64_t)w * px;
-    a.w = w; a.h = h; a.mx = mx; a.my = my; a.filter2d = filter2d;
-    mc_call_bd(a, bpc, bitdepth_max);
-    if (mi::launch_mc_call(a, 0, s)) return -EIO;
-    return win_out(dst, dst_stride, dout, 0, h, 0, (ptrdiff_t)w * px, s);
-}
-
-int mi_dsp_mc_prep(int filter2d, int16_t *tmp, const void *src, ptrdiff_t src_stride, int w, int h, int mx, int my,
-                   int bitdepth_max) {
-    const int bpc = bpc_of(bitdepth_max);
-    if (!bpc || !tmp || !src || filter2d < 0 || filter2d > 9 || !mc_dims_ok(w, h) || mx < 0 || mx > 15 || my < 0 ||
-        my > 15)
-        return -EINVAL;
-    std::lock_guard<std::mutex> lk(g_call.mu);
-    if (int e = g_call.init()) return e;
-    const int px = bpc == 8 ? 1 : 2;
-    hipStream_t s = g_call.stream;
-    const int r0 = filter2d == 9 ? 0 : -3, r1 = h + (filter2d == 9 ? 1 : 5);
-    const ptrdiff_t b0 = (filter2d == 9 ? 0 : -3) * px, b1 = (ptrdiff_t)(w + (filter2d == 9 ? 1 : 5)) * px;
-    uint8_t *win = g_call.scratch;
-    int16_t *dtmp = (int16_t *)(win + (1 << 19));
-    if (int e = win_in(win, src, src_stride, r0, r1, b0, b1, s)) return e;
-    mi::McCallArgs a;
-    memset(&a, 0, sizeof(a));
-    a.src = win + (size_t)(-r0) * (b1 - b0) - b0;
-    a.src_stride = b1 - b0;
-    a.tmp1 = dtmp;
-    a.prep = 1;
-    a.w = w; a.h = h; a.mx = mx; a.my = my; a.filter2d = filter2d;
-    mc_call_bd(a, bpc, bitdepth_max);
-    if (mi::launch_mc_call(a, 0, s)) return -EIO;
-    if (hipMemcpyAsync(tmp, dtmp, (size_t)w * h * 2, hipMemcpyDefault, s) != hipSuccess) return -EIO;
-    return hipStreamSynchronize(s) == hipSuccess ? 0 : -EIO;
-}
-
-namespace {
-// avg / w_avg / mask / w_mask / blend*: op as mc_call_comb_kernel
-int mc_combine(int op, void *dst, ptrdiff_t ds, const int16_t *t1, const int16_t *t2, const void *tmp_px,
-               int w, int h, const uint8_t *mask, uint8_t *mask_out, int weight, int sign, int layout, int bdmax) {
-    const int bpc = bpc_of(bdmax);
-    if (!bpc || !dst || !mc_dims_ok(w, h)) return -EINVAL;
-    if ((op <= 3 && (!t1 || !t2)) || ((op == 2 || op == 4) && !mask) || (op == 3 && !mask_out) ||
-        (op >= 4 && !tmp_px) || (op == 3 && (layout < 1 || layout > 3)))
-        return -EINVAL;
-    std::lock_guard<std::mutex> lk(g_call.mu);
-    if (int e = g_call.init()) return e;
-    const int px = bpc == 8 ? 1 : 2;
-    hipStream_t s = g_call.stream;
-    const size_t n = (size_t)w * h;
-    uint8_t *dd = g_call.scratch, *d1 = dd + 65536, *d2 = d1 + 65536, *dm = d2 + 65536, *dmo = dm + 16384,
-            *dt = dmo + 16384;
-    mi::McCallArgs a;
-    memset(&a, 0, sizeof(a));
-    int e = 0;
-    if (op <= 3) {
-        e = copy_in(d1, t1, n * 2, s);
-        if (!e) e = copy_in(d2, t2, n * 2, s);
-    }
-    if (!e && (op == 2 || op == 4)) e = copy_in(dm, mask, n, s);
-    if (!e && op >= 4) e = copy_in(dt, tmp_px, n * px, s);
-    if (!e && op >= 4) e = win_in(dd, dst, ds, 0, h, 0, (ptrdiff_t)w * px, s);   // blends read dst
-    if (e) return e;
-    a.dst = dd;
-    a.dst_stride = (int64_t)w * px;
-    a.tmp1 = (int16_t *)d1;
-    a.tmp2 = (const int16_t *)d2;
-    a.mask = dm;
-    a.mask_out = dmo;
-    a.src = dt;
-    a.w = w; a.h = h; a.op = op; a.weight = weight; a.sign = sign;
-    a.ss_hor = layout == 1 || layout == 2;
-    a.ss_ver = layout == 1;
-    mc_call_bd(a, bpc, bdmax);
-    if (mi::launch_mc_call(a, 1, s)) return -EIO;
-    if (op == 3 && hipMemcpyAsync(mask_out, dmo, (size_t)(w >> a.ss_hor) * (h >> a.ss_ver), hipMemcpyDefault, s) != hipSuccess)
-        return -EIO;
-    return win_out(dst, ds, dd, 0, h, 0, (ptrdiff_t)w * px, s);
-}
-}  // namespace
-
-int mi_dsp_mc_avg(void *dst, ptrdiff_t dst_stride, const int16_t *tmp1, const int16_t *tmp2, int w, int h,
-                  int bitdepth_max) {
-    return mc_combine(0, dst, dst_stride, tmp1, tmp2, nullptr, w, h, nullptr, nullptr, 0, 0, 0, bitdepth_max);
-}
-int mi_dsp_mc_w_avg(void *dst, ptrdiff_t dst_stride, const int16_t *tmp1, const int16_t *tmp2, int w, int h, int weight,
-                    int bitdepth_max) {
-    return mc_combine(1, dst, dst_stride, tmp1, tmp2, nullptr, w, h, nullptr, nullptr, weight, 0, 0, bitdepth_max);
-}
-int mi_dsp_mc_mask(void *dst, ptrdiff_t dst_stride, const int16_t *tmp1, const int16_t *tmp2, int w, int h,
-                   const uint8_t *mask, int bitdepth_max) {
-    return mc_combine(2, dst, dst_stride, tmp1, tmp2, nullptr, w, h, mask, nullptr, 0, 0, 0, bitdepth_max);
-}
-int mi_dsp_mc_w_mask(int layout, void *dst, ptrdiff_t dst_stride, const int16_t *tmp1, const int16_t *tmp2, int w,
-                     int h, uint8_t *mask, int sign, int bitdepth_max) {
-    return mc_combine(3, dst, dst_stride, tmp1, tmp2, nullptr, w, h, nullptr, mask, 0, sign, layout, bitdepth_max);
-}
-int mi_dsp_mc_blend(void *dst, ptrdiff_t dst_stride, const void *tmp, int w, int h, const uint8_t *mask,
-                    int bitdepth_max) {
-    return mc_combine(4, dst, dst_stride, nullptr, nullptr, tmp, w, h, mask, nullptr, 0, 0, 0, bitdepth_max);
-}
-int mi_dsp_mc_blend_v(void *dst, ptrdiff_t dst_stride, const void *tmp, int w, int h, int bitdepth_max) {
-    return mc_combine(5, dst, dst_stride, nullptr, nullptr, tmp, w, h, nullptr, nullptr, 0, 0, 0, bitdepth_max);
-}
-int mi_dsp_mc_blend_h(void *dst, ptrdiff_t dst_stride, const void *tmp, int w, int h, int bitdepth_max) {
-    return mc_combine(6, dst, dst_stride, nullptr, nullptr, tmp, w, h, nullptr, nullptr, 0, 0, 0, bitdepth_max);
-}
-
-int mi_dsp_mc_emu_edge(int bw, int bh, int iw, int ih, int x, int y, void *dst, ptrdiff_t dst_stride, const void *ref,
-                       ptrdiff_t ref_stride, int bitdepth_max) {
-    const int bpc = bpc_of(bitdepth_max);
-    if (!bpc || !dst || !ref || bw < 1 || bh < 1 || bw > 256 || bh > 256 || iw < 1 || ih < 1) return -EINVAL;
-    std::lock_guard<std::mutex> lk(g_call.mu);
-    if (int e = g_call.init()) return e;
-    const int px = bpc == 8 ? 1 : 2;
-    hipStream_t s = g_call.stream;
-    auto clip = [](int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; };
-    // the reference pixels the block can reach: the clamped rectangle
-    const int ry0 = clip(y, 0, ih - 1), ry1 = clip(y + bh - 1, 0, ih - 1) + 1;
-    const int rx0 = clip(x, 0, iw - 1), rx1 = clip(x + bw - 1, 0, iw - 1) + 1;
-    uint8_t *win = g_call.scratch, *dout = win + (1 << 19);
-    if (int e = win_in(win, (const uint8_t *)ref + (ptrdiff_t)ry0 * ref_stride + (ptrdiff_t)rx0 * px, ref_stride, 0,
-                       ry1 - ry0, 0, (ptrdiff_t)(rx1 - rx0) * px, s))
-        return e;
-    mi::McCallArgs a;
-    memset(&a, 0, sizeof(a));
-    a.src = win;
-    a.src_stride = (int64_t)(rx1 - rx0) * px;
-    a.dst = dout;
-    a.dst_stride = (int64_t)bw * px;
-    a.w = bw; a.h = bh; a.mx = x; a.my = y; a.iw = iw; a.ih = ih;
-    mc_call_bd(a, bpc, bitdepth_max);
-    if (mi::launch_mc_call(a, 2, s)) return -EIO;
-    return win_out(dst, dst_stride, dout, 0, bh, 0, (ptrdiff_t)bw * px, s);
-}
-
-int mi_dsp_mc_warp8x8(int prep, void *dst, ptrdiff_t dst_stride, const void *src, ptrdiff_t src_stride,
-                      const int16_t *abcd, int mx, int my, int bitdepth_max) {
-    const int bpc = bpc_of(bitdepth_max);
-    if (!bpc || !dst || !src || !abcd) return -EINVAL;
-    std::lock_guard<std::mutex> lk(g_call.mu);
-    if (int e = g_call.init()) return e;
-    const int px = bpc == 8 ? 1 : 2;
-    hipStream_t s = g_call.stream;
-    int16_t hb[4];
-    if (hipMemcpy(hb, abcd, sizeof(hb), hipMemcpyDefault) != hipSuccess) return -EIO;
-    uint8_t *win = g_call.scratch, *dout = win + 4096;
-    const int r0 = -3, r1 = 12;
-    const ptrdiff_t b0 = -3 * px, b1 = 12 * px;
-    if (int e = win_in(win, src, src_stride, r0, r1, b0, b1, s)) return e;
-    mi::McCallArgs a;
-    memset(&a, 0, sizeof(a));
-    a.src = win + (size_t)(-r0) * (b1 - b0) - b0;
-    a.src_stride = b1 - b0;
-    a.dst = dout;
-    a.dst_stride = 8 * px;
-    a.tmp1 = (int16_t *)dout;
-    a.prep = prep;
-    a.w = 8; a.h = 8; a.mx = mx; a.my = my;
-    for (int i = 0; i < 4; i++) a.abcd[i] = hb[i];
-    mc_call_bd(a, bpc, bitdepth_max);
-    if (mi::launch_mc_call(a, 3, s)) return -EIO;
-    // warp8x8t: dst is the int16 intermediate with stride dst_stride (in elements, as the
-    // reference's tmp_stride); warp8x8: pixels
-    if (prep) return win_out(dst, dst_stride * 2, dout, 0, 8, 0, 16, s);
-    return win_out(dst, dst_stride, dout, 0, 8, 0, 8 * px, s);
-}
-
-int mi_dsp_mc_resize(void *dst, ptrdiff_t dst_stride, const void *src, ptrdiff_t src_stride, int dst_w, int h,
-                     int src_w, int dx, int mx0, int bitdepth_max) {
-    const int bpc = bpc_of(bitdepth_max);
-    if (!bpc || !dst || !src || dst_w < 1 || h < 1 || src_w < 1 || dst_w > 8192 || src_w > 8192 || h > 64 ||
-        mx0 < 0 || mx0 >= (1 << 14))
-        return -EINVAL;
-    std::lock_guard<std::mutex> lk(g_call.mu);
-    if (int e = g_call.init()) return e;
-    const int px = bpc == 8 ? 1 : 2;
-    if ((size_t)(src_w + dst_w) * h * px > (1u << 20)) return -EINVAL;
-    hipStream_t s = g_call.stream;
-    uint8_t *win = g_call.scratch, *dout = win + (size_t)src_w * h * px;
-    if (int e = win_in(win, src, src_stride, 0, h, 0, (ptrdiff_t)src_w * px, s)) return e;
-    mi::McCallArgs a;
-    memset(&a, 0, sizeof(a));
-    a.src = win;
-    a.src_stride = (int64_t)src_w * px;
-    a.dst = dout;
-    a.dst_stride = (int64_t)dst_w * px;
-    a.w = dst_w; a.h = h; a.iw = src_w; a.mx = mx0; a.weight = dx;
-    mc_call_bd(a, bpc, bitdepth_max);
-    if (mi::launch_mc_call(a, 4, s)) return -EIO;
-    return win_out(dst, dst_stride, dout, 0, h, 0, (ptrdiff_t)dst_w * px, s);
-}
-
-int mi_dsp_mc_scaled(int prep, int filter2d, void *dst, ptrdiff_t dst_stride, const void *src, ptrdiff_t src_stride,
-                     int w, int h, int mx, int my, int dx, int dy, int bitdepth_max) {
-    const int bpc = bpc_of(bitdepth_max);
-    if (!bpc || !dst || !src || filter2d < 0 || filter2d > 9 || !mc_dims_ok(w, h) || mx < 0 || mx >= 1024 || my < 0 ||
-        my >= 1024 || dx < 1 || dy < 1 || dx > 2048 || dy > 2048)
-        return -EINVAL;
-    std::lock_guard<std::mutex> lk(g_call.mu);
-    if (int e = g_call.init()) return e;
-    const int px = bpc == 8 ? 1 : 2;
-    hipStream_t s = g_call.stream;
-    // source reach: rows -3 .. ((h-1)*dy + my >> 10) + 4, columns -3 .. ((w-1)*dx + mx >> 10) + 4
-    const int r0 = -3, r1 = (((h - 1) * dy + my) >> 10) + 5;
-    const ptrdiff_t b0 = -3 * px, b1 = (ptrdiff_t)((((w - 1) * dx + mx) >> 10) + 5) * px;
-    if ((size_t)(r1 - r0) * (b1 - b0) > (1u << 19)) return -EINVAL;
-    uint8_t *win = g_call.scratch, *dout = win + (1 << 19);
-    if (int e = win_in(win, src, src_stride, r0, r1, b0, b1, s)) return e;
-    mi::McCallArgs a;
-    memset(&a, 0, sizeof(a));
-    a.src = win + (size_t)(-r0) * (b1 - b0) - b0;
-    a.src_stride = b1 - b0;
-    a.dst = dout;
-    a.dst_stride = (int64_t)w * px;
-    a.tmp1 = (int16_t *)dout;
-    a.prep = prep;
-    a.w = w; a.h = h; a.mx = mx; a.my = my; a.dx = dx; a.dy = dy; a.filter2d = filter2d;
-    mc_call_bd(a, bpc, bitdepth_max);
-    if (mi::launch_mc_call(a, 5, s)) return -EIO;
-    if (prep) {
-        if (hipMemcpyAsync(dst, dout, (size_t)w * h * 2, hipMemcpyDefault, s) != hipSuccess) return -EIO;
-        return hipStreamSynchronize(s) == hipSuccess ? 0 : -EIO;
-    }
-    return win_out(dst, dst_stride, dout, 0, h, 0, (ptrdiff_t)w * px, s);
-}
-
-// ---- lr table (src/looprestoration.rs:91-107): wiener, sgr[kind] on one unit ----
-namespace {
-// Stage the unit's pixels (columns 0 .. w + 3*have_right), the lpf rows 0, 1, 6, 7 (columns
-// -3*have_left .. w + 3*have_right) and left[h][4] into one pitch-P buffer (column 3 = x 0),
-// filter, and write the w x h result back over p.
-int lr_call(mi::LrCallArgs &a, void *p, ptrdiff_t stride, const void *left, const void *lpf, int w, int h,
-            int edges, int bitdepth_max, int bpc) {
-    const int px = bpc == 8 ? 1 : 2;
-    const bool hl = edges & 1, hr = edges & 2, ht = edges & 4, hb = edges & 8;
-    if ((hl && !left) || ((ht || hb) && !lpf)) return -EINVAL;
-    hipStream_t s = g_call.stream;
-    const ptrdiff_t P = (ptrdiff_t)(w + 6) * px;
-    uint8_t *dp = g_call.scratch, *dlpf = dp + 64 * P, *dleft = dlpf + 8 * P, *dout = dleft + 64 * 4 * 2;
-    auto rows = [&](uint8_t *dst, const void *src, int r, ptrdiff_t c0, ptrdiff_t c1) -> int {
-        return hipMemcpyAsync(dst + r * P + 3 * px + c0, (const uint8_t *)src + r * stride + c0, c1 - c0,
-                              hipMemcpyDefault, s) == hipSuccess ? 0 : -EIO;
-    };
-    const ptrdiff_t c1 = (ptrdiff_t)(w + (hr ? 3 : 0)) * px, lc0 = hl ? -3 * px : 0;
-    int e = 0;
-    for (int r = 0; r < h && !e; r++) e = rows(dp, p, r, 0, c1);
-    if (ht) for (int r = 0; r < 2 && !e; r++) e = rows(dlpf, lpf, r, lc0, c1);
-    if (hb) for (int r = 6; r < 8 && !e; r++) e = rows(dlpf, lpf, r, lc0, c1);
-    if (!e && hl) e = copy_in(dleft, left, (size_t)h * 4 * px, s);
-    if (e) return e;
-    a.p = dp + 3 * px;
-    a.lpf = dlpf + 3 * px;
-    a.left = dleft;
-    a.out = dout;
-    a.ps = P / px;
-    a.w = w;
-    a.h = h;
-    a.edges = edges;
-    a.bd = bpc;
-    (void)bitdepth_max;
-    if (mi::launch_lr_call(a, bpc, s)) return -EIO;
-    return win_out(p, stride, dout, 0, h, 0, (ptrdiff_t)w * px, s);
-}
-bool lr_dims_ok(int w, int h) { return w >= 1 && w <= 384 && h >= 1 && h <= 64; }
-}  // namespace
-
-int mi_dsp_lr_wiener(void *p, ptrdiff_t stride, const void *left, const void *lpf, int w, int h, const void *params,
-                     int edges, int bitdepth_max) {
-    const int bpc = bpc_of(bitdepth_max);
-    if (!bpc || !p || !params || !lr_dims_ok(w, h) || edges < 0 || edges > 15) return -EINVAL;
-    std::lock_guard<std::mutex> lk(g_call.mu);
-    if (int e = g_call.init()) return e;
-    int16_t f[2][8];
-    if (hipMemcpy(f, params, sizeof(f), hipMemcpyDefault) != hipSuccess) return -EIO;
-    mi::LrCallArgs a;
-    memset(&a, 0, sizeof(a));
-    a.tp.wiener = true;
-    for (int k = 0; k < 7; k++) { a.tp.fh[k] = f[0][k]; a.tp.fv[k] = f[1][k]; }
-    if (bpc == 8) a.tp.fh[3] += 128;   // the reference adds the 8-bit centre tap separately
-    return lr_call(a, p, stride, left, lpf, w, h, edges, bitdepth_max, bpc);
-}
-
-int mi_dsp_lr_sgr(int kind, void *p, ptrdiff_t stride, const void *left, const void *lpf, int w, int h,
-                  const void *params, int edges, int bitdepth_max) {
-    const int bpc = bpc_of(bitdepth_max);
-    if (!bpc || kind < 0 || kind > 2 || !p || !params || !lr_dims_ok(w, h) || edges < 0 || edges > 15) return -EINVAL;
-    std::lock_guard<std::mutex> lk(g_call.mu);
-    if (int e = g_call.init()) return e;
-    struct { uint32_t s0, s1; int16_t w0, w1; } sp;   // LooprestorationParams_sgr
-    if (hipMemcpy(&sp, params, sizeof(sp), hipMemcpyDefault) != hipSuccess) return -EIO;
-    mi::LrCallArgs a;
-    memset(&a, 0, sizeof(a));
-    a.tp.wiener = false;
-    a.tp.s0 = kind != 1 ? (int)sp.s0 : 0;
-    a.tp.s1 = kind != 0 ? (int)sp.s1 : 0;
-    a.tp.w0 = sp.w0;
-    a.tp.w1 = sp.w1;
-    if ((kind != 1 && !a.tp.s0) || (kind != 0 && !a.tp.s1)) return -EINVAL;
-    return lr_call(a, p, stride, left, lpf, w, h, edges, bitdepth_max, bpc);
-}
-
-
-// ---- film-grain table (src/filmgrain.rs:41-198): generate_grain_y / _uv, fgy / fguv_32x32xn ----
-namespace {
-constexpr int kGW = 82, kGH = 73, kGP = 88;   // template width / height, device pitch (fg.hip)
-constexpr size_t kFgLutB = 3 * kGH * kGP * 2, kFgSclB = 3 * 4096;
-size_t al256(size_t n) { return (n + 255) & ~(size_t)255; }
-
-int fg_read_data(MiFilmGrainData &d, const MiFilmGrainData *data) {
-    if (hipMemcpy(&d, data, sizeof(d), hipMemcpyDefault) != hipSuccess) return -EIO;
-    return fg_data_ok(&d) ? 0 : -EINVAL;
-}
-// caller's GrainLut<Entry> rows (82 entries: int8 at 8 bits, int16 above) <-> int16 [73][82]
-int fg_lut_read(int16_t *t, const void *buf, int bpc) {
-    if (bpc == 8) {
-        int8_t b[kGH * kGW];
-        if (hipMemcpy(b, buf, sizeof(b), hipMemcpyDefault) != hipSuccess) return -EIO;
-        for (int i = 0; i < kGH * kGW; i++) t[i] = b[i];
-        return 0;
-    }
-    return hipMemcpy(t, buf, kGH * kGW * 2, hipMemcpyDefault) == hipSuccess ? 0 : -EIO;
-}
-int fg_lut_write(void *buf, const int16_t *t, int bpc) {
-    if (bpc == 8) {
-        int8_t b[kGH * kGW];
-        for (int i = 0; i < kGH * kGW; i++) b[i] = (int8_t)t[i];
-        return hipMemcpy(buf, b, sizeof(b), hipMemcpyDefault) == hipSuccess ? 0 : -EIO;
-    }
-    return hipMemcpy(buf, t, kGH * kGW * 2, hipMemcpyDefault) == hipSuccess ? 0 : -EIO;
-}
-// run the template generator and fetch plane pl's template into t [73][82]
-int fg_generate(mi::FgArgs &a, int pl, int16_t *t) {
-    hipStream_t s = g_call.stream;
-    a.lut = (int16_t *)g_call.scratch;
-    a.scaling = g_call.scratch + kFgLutB;
-    if (mi::launch_fg(a, s, true, false)) return -EIO;
-    static int16_t dev[kGH * kGP];
-    if (hipMemcpyAsync(dev, a.lut + pl * kGH * kGP, sizeof(dev), hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess)
-        return -EIO;
-    for (int r = 0; r < kGH; r++) memcpy(t + r * kGW, dev + r * kGP, kGW * 2);
-    return 0;
-}
-// the caller's template -> device slot pl (pitch 88)
-int fg_lut_in(int16_t *dlut, int pl, const void *grain_lut, int bpc, hipStream_t s) {
-    static int16_t t[kGH * kGW], dev[kGH * kGP];
-    if (int e = fg_lut_read(t, grain_lut, bpc)) return e;
-    memset(dev, 0, sizeof(dev));
-    for (int r = 0; r < kGH; r++) memcpy(dev + r * kGP, t + r * kGW, kGW * 2);
-    if (hipMemcpyAsync(dlut + pl * kGH * kGP, dev, sizeof(dev), hipMemcpyHostToDevice, s) != hipSuccess) return -EIO;
-    return hipStreamSynchronize(s) == hipSuccess ? 0 : -EIO;   // dev is reused
-}
-int layout_ok(int layout) { return layout >= 1 && layout <= 3; }
-
-// fgy (plane 0) / fguv (plane 1 + uv): one 32-row strip through the frame apply kernel
-int fg_strip(int pl, int layout, void *dst_row, const void *src_row, ptrdiff_t stride, const MiFilmGrainData *data,
-             size_t pw, const uint8_t *scaling, const void *grain_lut, int bh, int row_num, const void *luma_row,
-             ptrdiff_t luma_stride, int is_id, int bitdepth_max) {
-    const int bpc = bpc_of(bitdepth_max);
-    const int sx = pl && layout != 3, sy = pl && layout == 1;
-    if (!bpc || !dst_row || !src_row || !data || !scaling || !grain_lut || (pl && (!luma_row || !layout_ok(layout))) ||
-        pw < 1 || pw > 8192 || bh < 1 || bh > (32 >> sy) || row_num < 0)
-        return -EINVAL;
-    std::lock_guard<std::mutex> lk(g_call.mu);
-    if (int e = g_call.init()) return e;
-    if (int e = fg_tables()) return e;
-    mi::FgArgs a;
-    memset(&a, 0, sizeof(a));
-    if (int e = fg_read_data(a.data, data)) return e;
-    const int px = bpc == 8 ? 1 : 2;
-    const size_t P = al256(pw * px), lw = pw << sx, LP = al256(lw * px);
-    const int lrows = pl ? ((bh - 1) << sy) + 1 : 0;
-    const int nblocks = (int)((pw + (32 >> sx) - 1) / (32 >> sx));
-    const size_t o_scl = kFgLutB, o_off = o_scl + kFgSclB, o_src = o_off + al256(2 * nblocks),
-                 o_luma = o_src + P * bh, total = o_luma + LP * lrows;
-    if (int e = g_call.reserve(total)) return e;
-    hipStream_t s = g_call.stream;
-    uint8_t *S = g_call.scratch;
-    a.lut = (int16_t *)S;
-    a.scaling = S + o_scl;
-    a.offsets = S + o_off;
-    if (int e = fg_lut_in(a.lut, pl, grain_lut, bpc, s)) return e;
-    int e = copy_in(a.scaling + pl * 4096, scaling, (size_t)1 << bpc, s);
-    if (!e && pl) e = copy_in(a.scaling, scaling, (size_t)1 << bpc, s);   // the slot read under chroma_scaling_from_luma
-    for (int r = 0; r < bh && !e; r++)
-        if (hipMemcpyAsync(S + o_src + r * P, (const uint8_t *)src_row + r * stride, pw * px, hipMemcpyDefault, s) !=
-            hipSuccess)
-            e = -EIO;
-    for (int y = 0; pl && y < bh && !e; y++)
-        if (hipMemcpyAsync(S + o_luma + (size_t)(y << sy) * LP, (const uint8_t *)luma_row + (y << sy) * luma_stride,
-                           lw * px, hipMemcpyDefault, s) != hipSuccess)
-            e = -EIO;
-    if (e) return e;
-    a.bpc = bpc;
-    a.layout = pl ? layout : 0;
-    a.ss_x = pl && layout != 3;
-    a.ss_y = pl && layout == 1;
-    a.w = (int)lw;
-    a.h = bh << sy;
-    a.is_id = is_id;
-    const bool prev = a.data.overlap_flag && row_num > 0;
-    a.nrows = prev ? 2 : 1;
-    a.row0 = prev ? row_num - 1 : row_num;
-    a.row_off = prev ? 1 : 0;
-    a.nblocks = nblocks;
-    a.src[0] = S + (pl ? o_luma : o_src);
-    a.stride[0] = pl ? (int64_t)LP : (int64_t)P;
-    a.src[pl] = S + o_src;
-    a.dst[pl] = S + o_src;
-    a.stride[pl] = (int64_t)P;
-    a.pw[pl] = (int)pw;
-    a.ph[pl] = bh;
-    a.chunks[pl] = (int)((pw + 511) / 512);
-    a.grain[pl] = 1;
-    const int nb = (a.chunks[pl] * bh + 4 * mi::kFgItems - 1) / (4 * mi::kFgItems);
-    for (int q = 0; q < 4; q++) a.blk_start[q] = q <= pl ? 0 : nb;
-    if (mi::launch_fg_call(a, s)) return -EIO;
-    for (int r = 0; r < bh && !e; r++)
-        if (hipMemcpyAsync((uint8_t *)dst_row + r * stride, S + o_src + r * P, pw * px, hipMemcpyDefault, s) != hipSuccess)
-            e = -EIO;
-    if (hipStreamSynchronize(s) != hipSuccess) return -EIO;
-    return e;
-}
-}  // namespace
-
-int mi_dsp_fg_generate_grain_y(void *buf, const MiFilmGrainData *data, int bitdepth_max) {
-    const int bpc = bpc_of(bitdepth_max);
-    if (!bpc || !buf || !data) return -EINVAL;
-    std::lock_guard<std::mutex> lk(g_call.mu);
-    if (int e = g_call.init()) return e;
-    if (int e = fg_tables()) return e;
-    mi::FgArgs a;
-    memset(&a, 0, sizeof(a));
-    if (int e = fg_read_data(a.data, data)) return e;
-    a.bpc = bpc;
-    static int16_t t[kGH * kGW];
-    if (int e = fg_generate(a, 0, t)) return e;
-    return fg_lut_write(buf, t, bpc);
-}
-
-int mi_dsp_fg_generate_grain_uv(int layout, void *buf, const void *buf_y, const MiFilmGrainData *data, int uv,
-                                int bitdepth_max) {
-    const int bpc = bpc_of(bitdepth_max);
-    if (!bpc || !layout_ok(layout) || !buf || !buf_y || !data || uv < 0 || uv > 1) return -EINVAL;
-    std::lock_guard<std::mutex> lk(g_call.mu);
-    if (int e = g_call.init()) return e;
-    if (int e = fg_tables()) return e;
-    mi::FgArgs a;
-    memset(&a, 0, sizeof(a));
-    if (int e = fg_read_data(a.data, data)) return e;
-    static int16_t ty[kGH * kGW], t[kGH * kGW], out[kGH * kGW];
-    if (int e = fg_lut_read(ty, buf_y, bpc)) return e;
-    int16_t *dly = (int16_t *)(g_call.scratch + kFgLutB + kFgSclB);
-    if (hipMemcpy(dly, ty, sizeof(ty), hipMemcpyHostToDevice) != hipSuccess) return -EIO;
-    a.bpc = bpc;
-    a.layout = layout;
-    a.ss_x = layout != 3;
-    a.ss_y = layout == 1;
-    a.lut_y = dly;
-    a.uv_only = 1 + uv;
-    if (int e = fg_generate(a, 1 + uv, t)) return e;
-    // only the chroma template's own cw x chh corner is written, as the reference does
-    if (int e = fg_lut_read(out, buf, bpc)) return e;
-    const int cw = a.ss_x ? 44 : kGW, chh = a.ss_y ? 38 : kGH;
-    for (int r = 0; r < chh; r++) memcpy(out + r * kGW, t + r * kGW, cw * 2);
-    return fg_lut_write(buf, out, bpc);
-}
-
-int mi_dsp_fgy_32x32xn(void *dst_row, const void *src_row, ptrdiff_t stride, const MiFilmGrainData *data, size_t pw,
-                       const uint8_t *scaling, const void *grain_lut, int bh, int row_num, int bitdepth_max) {
-    return fg_strip(0, 0, dst_row, src_row, stride, data, pw, scaling, grain_lut, bh, row_num, nullptr, 0, 0,
-                    bitdepth_max);
-}
-
-int mi_dsp_fguv_32x32xn(int layout, void *dst_row, const void *src_row, ptrdiff_t stride,
-                        const MiFilmGrainData *data, size_t pw, const uint8_t *scaling, const void *grain_lut, int bh,
-                        int row_num, const void *luma_row, ptrdiff_t luma_stride, int uv_pl, int is_id,
-                        int bitdepth_max) {
-    if (uv_pl < 0 || uv_pl > 1) return -EINVAL;
-    return fg_strip(1 + uv_pl, layout, dst_row, src_row, stride, data, pw, scaling, grain_lut, bh, row_num, luma_row,
-                    luma_stride, is_id, bitdepth_max);
-}
-
 }  // extern "C"
-} // extern "C"
 
 namespace mi_internal {
 

@@ -147,4 +147,8 @@ namespace mi_internal {
 // blocks whose pixels are read beyond the edges (CfL luma, intra block copy sources)
 int intra_recon(MiCtx *ctx, const MiIntraFrame *frames, int nframes, const int32_t *strip_start, int nstrips,
                 unsigned flags, void *stream, bool granules = false);
+// What the film-grain entries of capi.cpp and dsp_calls.cpp share (capi.cpp): the kernels'
+// constant tables, uploaded once per process (0 or -EIO), and the parameter ranges they index with
+int fg_tables();
+bool fg_data_ok(const MiFilmGrainData *data);
 }

@@ -1,6 +1,6 @@
 // dsp_table.cpp — the slot-exact drop-in surface (include/mi_dsp_table.h): one void function
 // per Rav1dDSPContext slot with the slot's own signature, each a thunk over the per-call
-// entries (capi.cpp mi_dsp_*), and mi_fill_dsp_tables filling the reference's table layout as
+// entries (dsp_calls.cpp mi_dsp_*), and mi_fill_dsp_tables filling the reference's table layout as
 // its *_dsp_init functions do (src/decode.rs:4739-4774).
 //
 // The reference's slots return void and leave preconditions to the caller (assert /

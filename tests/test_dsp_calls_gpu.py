@@ -443,3 +443,319 @@ def test_fg_32x32xn(gpu, bpc):
         assert rc == 0
         assert np.array_equal(got[:, :pw], ref[:, :pw]), ("fg", it, pl, layout, pw, bh, row_num,
                                                            np.argwhere(got[:, :pw] != ref[:, :pw])[:4])
+
+
+# ---- host or device pointers, stride signs, the caller's device, the largest accepted sizes ----
+
+class _Bufs:
+    """Named numpy arrays placed in host memory, or (names in `dev`) as device tensors holding the
+    same bytes; p() is the pointer at a byte offset, get() the array as it now is."""
+
+    def __init__(self, arrays, dev=()):
+        import torch
+        self.host = {k: v.copy() for k, v in arrays.items()}
+        self.dev = {k: torch.from_numpy(self.host[k].reshape(-1).view(np.uint8)).cuda() for k in dev}
+
+    def p(self, name, off=0):
+        if name in self.dev:
+            return ctypes.c_void_p(self.dev[name].data_ptr() + off)
+        return ctypes.c_void_p(self.host[name].ctypes.data + off)
+
+    def get(self, name):
+        if name not in self.dev:
+            return self.host[name]
+        h = self.host[name]
+        return self.dev[name].cpu().numpy().view(h.dtype).reshape(h.shape)
+
+
+def _same_on_device(arrays, call, written, placements=None):
+    """call(bufs) -> rc with every buffer on the host, then per placement (default: every buffer
+    on the device): all buffers end byte-identical, and the destinations in `written` (name ->
+    boolean mask of the window the entry may write) keep their other bytes. Returns the host
+    buffers."""
+    host = _Bufs(arrays)
+    assert call(host) == 0
+    for name, mask in written.items():
+        assert np.array_equal(host.get(name)[~mask], arrays[name][~mask]), name
+    for dev in placements or [tuple(arrays)]:
+        b = _Bufs(arrays, dev)
+        assert call(b) == 0
+        for name in arrays:
+            assert np.array_equal(b.get(name), host.get(name)), (name, dev)
+    return host
+
+
+def _window(shape, y0, x0, h, w):
+    m = np.zeros(shape, bool)
+    m[y0:y0 + h, x0:x0 + w] = True
+    return m
+
+
+def _rand_px(rng, shape, bpc):
+    return rng.integers(0, 1 << bpc, size=shape).astype(_dt(bpc))
+
+
+@pytest.mark.parametrize("bpc", [8, 10])
+@pytest.mark.parametrize("dims", [(8, 8), (4, 16)])
+def test_device_pointers_itxfm_add(gpu, bpc, dims):
+    from rav1d_amd.synth import TX_BY_DIMS, make_coefs
+    rng = np.random.default_rng(1200 + bpc + dims[1])
+    w, h = dims
+    tx = TX_BY_DIMS[dims]
+    c, _ = make_coefs(rng, tx, 0, 2, bpc)
+    arrays = {"dst": _rand_px(rng, (h + 5, w + 9), bpc), "coef": c.astype(np.int16 if bpc == 8 else np.int32)}
+    assert arrays["coef"].any()
+    isz, pitch = arrays["dst"].itemsize, arrays["dst"].strides[0]
+
+    def call(b):
+        return lib().mi_dsp_itxfm_add(tx, 0, b.p("dst", 2 * pitch + 3 * isz), pitch, b.p("coef"), w * h - 1,
+                                      (1 << bpc) - 1)
+
+    host = _same_on_device(arrays, call, {"dst": _window(arrays["dst"].shape, 2, 3, h, w)},
+                           [("dst", "coef"), ("dst",), ("coef",)])
+    assert not host.get("coef").any()            # consumed coefficients are zeroed for the caller
+    assert not np.array_equal(host.get("dst"), arrays["dst"])
+
+
+@pytest.mark.parametrize("bpc", [8, 10])
+@pytest.mark.parametrize("mode,angle", [(0, 0), (7, 113 | 1 << 10)])
+def test_device_pointers_intra_pred(gpu, bpc, mode, angle):
+    rng = np.random.default_rng(1300 + bpc + mode)
+    arrays = {"dst": _rand_px(rng, (12, 20), bpc), "edge": _rand_px(rng, 65, bpc)}
+    isz, pitch = arrays["dst"].itemsize, arrays["dst"].strides[0]
+
+    def call(b):
+        return lib().mi_dsp_intra_pred(mode, b.p("dst", 3 * pitch + 5 * isz), pitch, b.p("edge", 32 * isz), 8, 8,
+                                       angle, 8, 8, (1 << bpc) - 1)
+
+    _same_on_device(arrays, call, {"dst": _window((12, 20), 3, 5, 8, 8)})
+
+
+@pytest.mark.parametrize("bpc", [8, 10])
+def test_device_pointers_cfl_ac_mc(gpu, bpc):
+    rng = np.random.default_rng(1400 + bpc)
+    bdmax = (1 << bpc) - 1
+    arrays = {"y": _rand_px(rng, (16, 21), bpc), "ac": np.full(64, 77, np.int16)}
+
+    def cfl_ac(b):
+        return lib().mi_dsp_cfl_ac(1, b.p("ac"), b.p("y"), arrays["y"].strides[0], 0, 0, 8, 8, bdmax)
+
+    _same_on_device(arrays, cfl_ac, {})
+    arrays = {"dst": _rand_px(rng, (12, 20), bpc), "src": make_texture(rng, 32, 32, bpc)}
+    isz, pitch, spitch = arrays["dst"].itemsize, arrays["dst"].strides[0], arrays["src"].strides[0]
+
+    def put(b):
+        return lib().mi_dsp_mc_put(0, b.p("dst", 3 * pitch + 5 * isz), pitch, b.p("src", 8 * spitch + 8 * isz),
+                                   spitch, 8, 8, 5, 5, bdmax)
+
+    _same_on_device(arrays, put, {"dst": _window((12, 20), 3, 5, 8, 8)})
+    # avg of two intermediates in prep's range: (pixel << intermediate bits) - bias
+    ib, bias = (4, 0) if bpc == 8 else (14 - bpc, 8192)
+    arrays = {"dst": _rand_px(rng, (12, 20), bpc)}
+    for k in ("t1", "t2"):
+        arrays[k] = ((rng.integers(0, 1 << bpc, size=64) << ib) - bias).astype(np.int16)
+
+    def avg(b):
+        return lib().mi_dsp_mc_avg(b.p("dst", 3 * pitch + 5 * isz), pitch, b.p("t1"), b.p("t2"), 8, 8, bdmax)
+
+    _same_on_device(arrays, avg, {"dst": _window((12, 20), 3, 5, 8, 8)})
+
+
+@pytest.mark.parametrize("bpc", [8, 10])
+@pytest.mark.parametrize("dir", [0, 1])
+def test_device_pointers_loop_filter_sb(gpu, bpc, dir):
+    rng = np.random.default_rng(1500 + bpc + dir)
+    # nearly flat with a small step at the filtered edge, so that the filters fire
+    yy, xx = np.mgrid[0:48, 0:48]
+    pic = ((60 + 6 * ((xx >= 16) ^ (yy >= 16)) + rng.integers(0, 2, size=(48, 48))) << (bpc - 8)).astype(_dt(bpc))
+    e, i = calc_eih(2)
+    lut = np.zeros(144, np.uint8)
+    lut[:64], lut[64:128] = e, i
+    b4_stride = 16
+    arrays = {"pic": pic, "vm": np.array([1, 2, 0], np.uint32), "lut": lut,      # 2 units: a 4- and an 8-wide edge
+              "lvl": rng.integers(32, 64, size=(8, b4_stride, 4)).astype(np.uint8)}
+    isz, pitch = pic.itemsize, pic.strides[0]
+
+    def call(b):
+        return lib().mi_dsp_loop_filter_sb(0, dir, b.p("pic", 16 * pitch + 16 * isz), pitch, b.p("vm"),
+                                           b.p("lvl", (2 * b4_stride + 3) * 4), b4_stride, b.p("lut"), 32,
+                                           (1 << bpc) - 1)
+
+    # 8 samples either side of the edge, 2 units of 4 along it
+    win = _window(pic.shape, 16, 8, 8, 16) if dir == 0 else _window(pic.shape, 8, 16, 16, 8)
+    host = _same_on_device(arrays, call, {"pic": win})
+    assert not np.array_equal(host.get("pic"), pic)
+
+
+@pytest.mark.parametrize("bpc", [8, 10])
+def test_device_pointers_lr_wiener(gpu, bpc):
+    rng = np.random.default_rng(1600 + bpc)
+    f = np.zeros((2, 8), np.int16)
+    for k in range(2):
+        t = [3, -7, 15]
+        f[k, :7] = [t[0], t[1], t[2], -2 * sum(t) + (128 if (k == 1 or bpc > 8) else 0), t[2], t[1], t[0]]
+    arrays = {"pic": make_texture(rng, 40, 24, bpc), "left": make_texture(rng, 4, 8, bpc),
+              "lpf": make_texture(rng, 40, 8, bpc), "f": f}
+    isz, pitch = arrays["pic"].itemsize, arrays["pic"].strides[0]
+
+    def call(b):
+        return lib().mi_dsp_lr_wiener(b.p("pic", 8 * pitch + 8 * isz), pitch, b.p("left"), b.p("lpf", 8 * isz), 16, 8,
+                                      b.p("f"), 15, (1 << bpc) - 1)
+
+    _same_on_device(arrays, call, {"pic": _window((24, 40), 8, 8, 8, 16)})
+
+
+@pytest.mark.parametrize("bpc", [8, 10])
+def test_device_pointers_fgy(gpu, bpc):
+    from rav1d_amd.frame import film_grain_data
+    from rav1d_amd.synth import make_fg_params
+    rng = np.random.default_rng(1700 + bpc)
+    gctr = 128 << (bpc - 8)
+    d = film_grain_data(make_fg_params(rng, 1))
+    arrays = {"dst": _rand_px(rng, (36, 96), bpc), "src": make_texture(rng, 96, 32, bpc),
+              "data": np.frombuffer(bytes(d), np.uint8), "scl": rng.integers(0, 256, size=1 << bpc).astype(np.uint8),
+              "lut": rng.integers(-gctr, gctr, size=(74, 82)).astype(_entry(bpc))}
+    isz, pitch = arrays["dst"].itemsize, arrays["dst"].strides[0]
+    assert arrays["src"].strides[0] == pitch     # the entry has one stride for both
+
+    def call(b):
+        return lib().mi_dsp_fgy_32x32xn(b.p("dst", 2 * pitch + 16 * isz), b.p("src", 16 * isz), pitch, b.p("data"), 64,
+                                        b.p("scl"), b.p("lut"), 32, 1, (1 << bpc) - 1)
+
+    _same_on_device(arrays, call, {"dst": _window((36, 96), 2, 16, 32, 64)})
+
+
+@pytest.mark.parametrize("bpc", [8, 10])
+def test_negative_strides_mc_put_intra_pred(gpu, bpc):
+    rng = np.random.default_rng(1800 + bpc)
+    bdmax = (1 << bpc) - 1
+    src = make_texture(rng, 32, 32, bpc)
+    flipped = np.ascontiguousarray(src[::-1])    # row r of src is row 31 - r: walked with a negative stride
+    isz, sp = src.itemsize, src.strides[0]
+    up, down, fsrc = (np.zeros((8, 11), _dt(bpc)) for _ in range(3))
+    dp = up.strides[0]
+    B = lambda a, off: ctypes.c_void_p(a.ctypes.data + off)    # at a byte offset
+    assert lib().mi_dsp_mc_put(0, B(up, 0), dp, B(src, 8 * sp + 8 * isz), sp, 8, 8, 5, 5, bdmax) == 0
+    assert lib().mi_dsp_mc_put(0, B(down, 7 * dp), -dp, B(src, 8 * sp + 8 * isz), sp, 8, 8, 5, 5, bdmax) == 0
+    assert lib().mi_dsp_mc_put(0, B(fsrc, 0), dp, B(flipped, 23 * sp + 8 * isz), -sp, 8, 8, 5, 5, bdmax) == 0
+    assert up[:, :8].any() and not up[:, 8:].any()
+    assert np.array_equal(down, up[::-1])
+    assert np.array_equal(fsrc, up)
+    edge = _rand_px(rng, 65, bpc)
+    for mode, angle in ((0, 0), (7, 113 | 1 << 10)):
+        up, down = np.zeros((8, 11), _dt(bpc)), np.zeros((8, 11), _dt(bpc))
+        assert lib().mi_dsp_intra_pred(mode, B(up, 0), dp, B(edge, 32 * isz), 8, 8, angle, 8, 8, bdmax) == 0
+        assert lib().mi_dsp_intra_pred(mode, B(down, 7 * dp), -dp, B(edge, 32 * isz), 8, 8, angle, 8, 8, bdmax) == 0
+        assert up[:, :8].any() and not up[:, 8:].any()
+        assert np.array_equal(down, up[::-1]), mode
+
+
+def test_callers_device_is_kept(gpu):
+    """The entries run on device 0 whatever device the calling thread has current, and leave
+    that device current."""
+    import torch
+    if torch.cuda.device_count() < 2:
+        pytest.skip("needs two GPUs")
+    from rav1d_amd.synth import TX_BY_DIMS, make_coefs
+    L = lib()                                    # (the HIP runtime's symbols resolve through the library)
+    rng = np.random.default_rng(1900)
+    t1, t2 = (((rng.integers(0, 1024, size=64) << 4) - 8192).astype(np.int16) for _ in range(2))
+    c0, _ = make_coefs(rng, TX_BY_DIMS[(8, 8)], 0, 2, 10)
+    d0 = _rand_px(rng, (8, 8), 10)
+
+    def run():
+        avg = np.zeros((8, 8), np.uint16)
+        assert L.mi_dsp_mc_avg(P(avg), 16, P(t1), P(t2), 8, 8, 1023) == 0
+        d, c = d0.copy(), c0.astype(np.int32)
+        assert L.mi_dsp_itxfm_add(TX_BY_DIMS[(8, 8)], 0, P(d), 16, P(c), 63, 1023) == 0
+        return avg, d, c
+
+    exp = run()
+    cur = ctypes.c_int(-1)
+    try:
+        assert L.hipSetDevice(1) == 0
+        got = run()
+        assert L.hipGetDevice(ctypes.byref(cur)) == 0 and cur.value == 1
+    finally:
+        L.hipSetDevice(0)
+    for g, e in zip(got, exp):
+        assert np.array_equal(g, e)
+
+
+def test_largest_sizes_mc(gpu):
+    """The largest accepted blocks at 12 bits: where two of a call's scratch buffers would overlap
+    if one were sized too small."""
+    o = _mc_sigs(_o())
+    I = ctypes.c_int
+    o.oracle_mc_resize.argtypes = [_VP, _SS, _VP, _SS, I, I, I, I, I, I]
+    o.oracle_mc_resize.restype = None
+    rng = np.random.default_rng(2000)
+    bpc, bdmax, w, h = 12, 4095, 128, 128
+    src = make_texture(rng, 144, 144, bpc)
+    off = 8 * 144 + 8
+    ref, got = np.zeros((h, w), np.uint16), np.zeros((h, w), np.uint16)
+    o.oracle_mc_put(0, P(ref), ref.strides[0], P(src, off), src.strides[0], w, h, 5, 5, bpc)
+    assert lib().mi_dsp_mc_put(0, P(got), got.strides[0], P(src, off), src.strides[0], w, h, 5, 5, bdmax) == 0
+    assert np.array_equal(got, ref)
+    t = [np.zeros(w * h, np.int16) for _ in range(2)]
+    gt = np.zeros(w * h, np.int16)
+    o.oracle_mc_prep(0, P(t[0]), P(src, off), src.strides[0], w, h, 5, 5, bpc)
+    assert lib().mi_dsp_mc_prep(0, P(gt), P(src, off), src.strides[0], w, h, 5, 5, bdmax) == 0
+    assert np.array_equal(gt, t[0])
+    o.oracle_mc_prep(4, P(t[1]), P(src, off + 3), src.strides[0], w, h, 9, 2, bpc)
+    m = rng.integers(0, 65, size=w * h).astype(np.uint8)
+    ref, got = np.zeros((h, w), np.uint16), np.zeros((h, w), np.uint16)
+    o.oracle_mc_mask(P(ref), ref.strides[0], P(t[0]), P(t[1]), w, h, P(m), bpc)
+    assert lib().mi_dsp_mc_mask(P(got), got.strides[0], P(t[0]), P(t[1]), w, h, P(m), bdmax) == 0
+    assert np.array_equal(got, ref)
+    dst0, tmp = make_texture(rng, w, h, bpc), make_texture(rng, w, h, bpc)
+    ref, got = dst0.copy(), dst0.copy()
+    o.oracle_mc_blend(P(ref), ref.strides[0], P(tmp), w, h, P(m), bpc)
+    assert lib().mi_dsp_mc_blend(P(got), got.strides[0], P(tmp), w, h, P(m), bdmax) == 0
+    assert np.array_equal(got, ref)
+    refpic = make_texture(rng, 300, 300, bpc)
+    r, g = np.zeros((256, 256), np.uint16), np.zeros((256, 256), np.uint16)
+    o.oracle_mc_emu_edge(256, 256, 300, 300, 22, 31, P(r), r.strides[0], P(refpic), refpic.strides[0], bpc)
+    assert lib().mi_dsp_mc_emu_edge(256, 256, 300, 300, 22, 31, P(g), g.strides[0], P(refpic), refpic.strides[0],
+                                    bdmax) == 0
+    assert np.array_equal(g, r)
+    # resize: (src_w + dst_w) * h * 2 bytes is exactly the 1 MiB the entry accepts, and neither
+    # buffer's size is a multiple of the scratch alignment; one more destination column is refused
+    src_w, dst_w, h = 3001, 5191, 64
+    dx = ((src_w << 14) + (dst_w >> 1)) // dst_w
+    s = make_texture(rng, src_w, h, bpc)
+    r, g = np.zeros((h, dst_w + 1), np.uint16), np.zeros((h, dst_w + 1), np.uint16)
+    o.oracle_mc_resize(P(r), r.strides[0], P(s), s.strides[0], dst_w, h, src_w, dx, 100, bpc)
+    assert lib().mi_dsp_mc_resize(P(g), g.strides[0], P(s), s.strides[0], dst_w, h, src_w, dx, 100, bdmax) == 0
+    assert np.array_equal(g, r)
+    assert lib().mi_dsp_mc_resize(P(g), g.strides[0], P(s), s.strides[0], dst_w + 1, h, src_w, dx, 100, bdmax) == -22
+    assert np.array_equal(g, r)
+
+
+def test_largest_sizes_lr(gpu):
+    o = _o()
+    I = ctypes.c_int
+    o.oracle_lr_wiener.argtypes = [_VP, _SS, _VP, _VP, I, I, _VP, I, I]
+    o.oracle_lr_wiener.restype = None
+    o.oracle_lr_sgr.argtypes = [I, _VP, _SS, _VP, _VP, I, I, ctypes.c_uint, ctypes.c_uint, I, I, I, I]
+    o.oracle_lr_sgr.restype = None
+    rng = np.random.default_rng(2100)
+    bpc, bdmax, w, h, off = 12, 4095, 384, 64, 8 * 400 + 8
+    pic, left, lpf = make_texture(rng, 400, 80, bpc), make_texture(rng, 4, h, bpc), make_texture(rng, 400, 8, bpc)
+    f = np.zeros((2, 8), np.int16)
+    for k in range(2):
+        t = [3 + k, -7, 15]
+        f[k, :7] = [t[0], t[1], t[2], -2 * sum(t) + 128, t[2], t[1], t[0]]
+    ref, got = pic.copy(), pic.copy()
+    o.oracle_lr_wiener(P(ref, off), ref.strides[0], P(left), P(lpf, 8), w, h, P(f), 15, bdmax)
+    assert lib().mi_dsp_lr_wiener(P(got, off), got.strides[0], P(left), P(lpf, 8), w, h, P(f), 15, bdmax) == 0
+    assert np.array_equal(got, ref)
+    s0, s1 = _SGR[3]                             # both radii: kind 2 (mix)
+    w0, w1 = -40, 128 - (-40 + 50)
+    prm = np.zeros(6, np.int16)
+    prm.view(np.uint32)[:2] = [s0, s1]
+    prm[4:6] = [w0, w1]
+    ref, got = pic.copy(), pic.copy()
+    o.oracle_lr_sgr(2, P(ref, off), ref.strides[0], P(left), P(lpf, 8), w, h, s0, s1, w0, w1, 15, bdmax)
+    assert lib().mi_dsp_lr_sgr(2, P(got, off), got.strides[0], P(left), P(lpf, 8), w, h, P(prm), 15, bdmax) == 0
+    assert np.array_equal(got, ref)
