@@ -332,10 +332,12 @@ __device__ __forceinline__ void predict_block(const IpredArgs &a, const MiIpredB
             lbase = w + h - 1;
             max_base_y = w + h - 1;
         } else {
-            // left = &topleft[-1]: store eb[lbase - k] = topleft[-1 - k], k in [0, w + h]
+            // left = &topleft[-1]: store eb[lbase - k] = topleft[-1 - k], k in [0, max_base_y]
+            // (all the interpolation reads; topleft[-1 - (w + h)] lies before the edge the
+            // caller owns, 2 (w + h) + 1 samples around topleft)
             lbase = w + h;
-            for (int k = lane; k <= w + h; k += 64) eb[lbase - k] = tl[-1 - k];
             max_base_y = h + min(w, h) - 1;
+            for (int k = lane; k <= max_base_y; k += 64) eb[lbase - k] = tl[-1 - k];
         }
         __syncthreads();
         const int base_inc = 1 + up;

@@ -267,3 +267,79 @@ def test_intra_recon_12bit_identity32_saturates(gpu, granules):
             bad = np.argwhere(got != exp[p])
             raise AssertionError(f"plane {p}: {len(bad)} mismatches, first at {bad[0]}: got {got[tuple(bad[0])]} "
                                  f"exp {exp[p][tuple(bad[0])]}")
+
+
+# ---- directed frames (tests/intra_cases.py): tiles, odd picture sizes, extreme pixels ----
+#
+# tests/test_intra_cases.py asserts without a GPU that every frame here holds a block of every
+# directed kind. Each case starts from a randomised picture, so an edge read from a pixel the
+# block must not see (beyond its tile, or beyond the coded area) gives another result than the
+# oracle's, and the whole allocated planes are compared, so a write outside a block shows too.
+
+def _directed(case):
+    """(frame, Frame on the device, initial planes, oracle prediction, oracle reconstruction)
+    of a case; the references are computed once and shared by the three tests."""
+    from tests import intra_cases as C
+    name, bpc, layout, _, _ = case
+    w, h = C.FRAMES[name][:2]
+    fr = C.case_frame(case)
+    cur = Frame(w, h, bpc, layout)
+    init, pred, rec = _directed_refs(case, tuple(cur.buffer_np(p).shape for p in range(len(cur.planes))))
+    return fr, cur, init, pred, rec
+
+
+_refs = {}
+
+
+def _directed_refs(case, shapes):
+    from tests import intra_cases as C
+    if case not in _refs:
+        bpc = case[1]
+        fr = C.case_frame(case)
+        init = C.case_init(case, shapes)
+        pred = oracle_lib.intra_blocks(init, bpc, fr["blocks"], fr["ac"], fr["idx"], fr["pal"])
+        rec, _ = oracle_lib.intra_recon(init, bpc, fr["blocks"], fr["tx_blocks"][fr["tx_of_block"]], fr["ac"],
+                                        fr["idx"], fr["pal"], fr["coef"])
+        _refs[case] = (init, pred, rec)
+    return _refs[case]
+
+
+def _same_planes(cur, exp, what):
+    for p in range(len(cur.planes)):
+        got = cur.buffer_np(p)
+        if not np.array_equal(got, exp[p]):
+            bad = np.argwhere(got != exp[p])
+            raise AssertionError(f"{what} plane {p}: {len(bad)} mismatches, first at {bad[0]}: got "
+                                 f"{got[tuple(bad[0])]} exp {exp[p][tuple(bad[0])]}")
+
+
+def _directed_cases():
+    from tests import intra_cases as C
+    return dict(argnames="case", argvalues=C.CASES, ids=C.case_id)
+
+
+@pytest.mark.parametrize(**_directed_cases())
+def test_intra_directed_per_level(gpu, case):
+    """Prediction only, one mi_intra_blocks launch per dependency level."""
+    fr, cur, init, pred, _ = _directed(case)
+    for p in range(len(cur.planes)):
+        cur.set_buffer_np(p, init[p])
+    run_intra_frame(gpu, cur, fr)
+    torch.cuda.synchronize()
+    _same_planes(cur, pred, "per level")
+
+
+@pytest.mark.parametrize("granules", [False, True])
+@pytest.mark.parametrize(**_directed_cases())
+def test_intra_directed_fused(gpu, case, granules):
+    """The persistent fused path with residuals, without and with MI_IR_EDGE_GRANULES, twice
+    over the same buffers (a new epoch must give the same picture)."""
+    from rav1d_amd.intra import IntraFrame, device_status
+    fr, cur, init, _, rec = _directed(case)
+    intra = IntraFrame(gpu, fr)
+    for rep in range(2):
+        for p in range(len(cur.planes)):
+            cur.set_buffer_np(p, init[p])
+        intra.recon(cur.picture(), granules=granules)
+        device_status(gpu)
+        _same_planes(cur, rec, f"rep {rep}")

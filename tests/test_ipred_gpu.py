@@ -8,9 +8,9 @@ import numpy as np
 import pytest
 import torch
 
-from rav1d_amd import IPRED_CFL, IPRED_PAL, lib
+from rav1d_amd import IPRED_CFL, IPRED_DTYPE, IPRED_PAL, lib
 from rav1d_amd.frame import Frame, _stream_ptr
-from rav1d_amd.ipred_synth import make_ipred_blocks
+from rav1d_amd.ipred_synth import EDGE_SPAN, SIZES, make_ipred_blocks
 from tests import oracle_lib
 
 pytestmark = pytest.mark.gpu
@@ -28,7 +28,11 @@ def oracle_block(b, edges, ac, idx, bpc):
 
 def run_batch(gpu, n, bpc, seed, modes=None):
     rng = np.random.default_rng(seed)
-    blocks, edges, ac, idx, rows = make_ipred_blocks(n, bpc, rng, modes=modes)
+    run_blocks(gpu, bpc, *make_ipred_blocks(n, bpc, rng, modes=modes))
+
+
+def run_blocks(gpu, bpc, blocks, edges, ac, idx, rows):
+    """One mi_ipred_blocks launch over the blocks; every block against the oracle."""
     f = Frame(4096, rows, bpc, 0)
     db = torch.from_numpy(blocks.view(np.uint8).copy()).cuda()
     de = torch.from_numpy(edges.view(np.uint8).copy()).cuda()
@@ -57,19 +61,20 @@ def test_ipred_batch_directional_and_filter(gpu, mode):
     run_batch(gpu, 800, 10, seed=100 + mode, modes=[mode])
 
 
-@pytest.mark.parametrize("bpc", [8, 10])
+@pytest.mark.parametrize("bpc", [8, 10, 12])
 def test_dsp_intra_pred_percall_host_pointers(gpu, bpc):
     rng = np.random.default_rng(7 + bpc)
     dt = np.uint8 if bpc == 8 else np.uint16
-    for _ in range(60):
+    for k in range(4 * len(SIZES)):
         mode = int(rng.integers(0, 14))
-        w, h = [(4, 4), (8, 8), (16, 8), (8, 32), (32, 32), (64, 16)][int(rng.integers(0, 6))]
+        w, h = SIZES[k % len(SIZES)]
         if mode == 13:
             w, h = min(w, 32), min(h, 32)
         angle = 0
         if mode in (6, 7, 8):
             from rav1d_amd.ipred_synth import random_angle
-            angle = random_angle(rng, mode) | (1 << 10)
+            # the edge filter on in even rounds over the sizes, off (the unfiltered edge) in odd ones
+            angle = random_angle(rng, mode) | ((~(k // len(SIZES)) & 1) << 10)
         elif mode == 13:
             angle = int(rng.integers(0, 5))
         e = rng.integers(0, 1 << bpc, size=261).astype(dt)
@@ -81,3 +86,139 @@ def test_dsp_intra_pred_percall_host_pointers(gpu, bpc):
         exp = oracle_lib.intra_pred(mode, e, 130, w, h, angle, w, h, bpc)
         assert np.array_equal(dst[:, :w], exp), (mode, w, h, angle)
         assert not dst[:, w:].any(), "wrote outside the block"
+
+
+# ---- exhaustive directional sweep and extreme pixels, one launch per test ----
+
+Z_ANGLES = sorted({b + 3 * d for b in (90, 180, 45, 135, 113, 157, 203, 67) for d in range(-3, 4)} - {90, 180})
+assert [sum(lo < a < hi for a in Z_ANGLES) for lo, hi in ((0, 90), (90, 180), (180, 270))] == [17, 27, 10]
+
+
+class Batch:
+    """Blocks laid out left to right in 64-row bands of the destination plane, each with an
+    edge buffer of its own (make_ipred_blocks's layout, with chosen instead of drawn contents)."""
+
+    def __init__(self, bpc):
+        self.bpc, self.bdmax = bpc, (1 << bpc) - 1
+        self.recs, self.edges, self.ac, self.idx = [], [], [np.zeros(1, np.int16)], [np.zeros(1, np.uint8)]
+        self.x = self.y = 0
+        self.n_ac = self.n_idx = 1
+
+    def add(self, mode, w, h, edge, angle=0, max_w=None, max_h=None, ac=None, idx=None, alpha=0):
+        assert len(edge) == EDGE_SPAN
+        if self.x + w > 4096:
+            self.x, self.y = 0, self.y + 64
+        aux = 0
+        if idx is not None:
+            aux, self.n_idx = self.n_idx, self.n_idx + w * h
+            self.idx.append(np.asarray(idx, np.uint8).reshape(w * h))
+        if ac is not None:
+            aux, self.n_ac = self.n_ac, self.n_ac + w * h
+            self.ac.append(np.asarray(ac, np.int16).reshape(w * h))
+        self.recs.append((len(self.recs) * EDGE_SPAN + 130, aux, self.x, self.y, w, h, 0, mode, angle,
+                          w if max_w is None else max_w, h if max_h is None else max_h, alpha, 0))
+        self.edges.append(edge)
+        self.x += w
+
+    def run(self, gpu):
+        dt = np.uint8 if self.bpc == 8 else np.uint16
+        run_blocks(gpu, self.bpc, np.array(self.recs, dtype=IPRED_DTYPE), np.concatenate(self.edges).astype(dt),
+                   np.concatenate(self.ac), np.concatenate(self.idx), self.y + 64)
+
+
+def edge_pattern(name, bdmax, rng=None):
+    """An edge buffer (EDGE_SPAN samples, topleft at 130; the top row above it, the left column
+    below it) of one pattern."""
+    i = np.arange(EDGE_SPAN)
+    if name == "random":
+        return rng.integers(0, bdmax + 1, size=EDGE_SPAN)
+    if name == "zero":
+        return np.zeros(EDGE_SPAN, np.int64)
+    if name == "max":
+        return np.full(EDGE_SPAN, bdmax, np.int64)
+    if name == "alternating":
+        return (i & 1) * bdmax
+    if name == "alternating_odd":
+        return (~i & 1) * bdmax
+    if name == "pairs":                      # 0 0 max max: the up-sampling taps (-1 9 9 -1) leave the range
+        return ((i >> 1) & 1) * bdmax
+    if name == "pairs_odd":
+        return (((i + 1) >> 1) & 1) * bdmax
+    if name == "top_max_left_zero":          # (the corner with the top)
+        return np.where(i >= 130, bdmax, 0)
+    if name == "top_zero_left_max":
+        return np.where(i >= 130, 0, bdmax)
+    if name == "ramp":
+        return (i * bdmax + (EDGE_SPAN - 1) // 2) // (EDGE_SPAN - 1)
+    raise ValueError(name)
+
+
+EXTREME_PATTERNS = ("zero", "max", "alternating", "alternating_odd", "pairs", "top_max_left_zero",
+                    "top_zero_left_max", "ramp")
+
+
+@pytest.mark.parametrize("edges", ["random", "alternating", "pairs"])
+@pytest.mark.parametrize("bpc", [8, 10, 12])
+def test_ipred_directional_sweep(gpu, bpc, edges):
+    """Every directional angle (17 of Z1, 27 of Z2, 10 of Z3) x every size x the four settings
+    of the smooth-neighbour and edge-filter bits (which decide the filter strength and the
+    up-sampling), Z2 also with the visible extent cut to 4 and to half the block; over random
+    edges, over edges alternating 0 / bdmax, and over pairs of 0 and of bdmax (0 0 max max: the
+    up-sampled edge's -1 9 9 -1 taps give 18 bdmax / 16 and -2 bdmax / 16, its clip at both ends)."""
+    rng = np.random.default_rng(900 + bpc)
+    bt = Batch(bpc)
+    for a in Z_ANGLES:
+        mode = 6 if a < 90 else 7 if a < 180 else 8
+        for w, h in SIZES:
+            ext = [(w, h)]
+            if mode == 7:
+                ext = sorted({(w, h), (4, h), (w, 4), (max(w // 2, 4), max(h // 2, 4))})
+            for bits in range(4):
+                for k, (mw, mh) in enumerate(ext):
+                    e = edge_pattern("random", bt.bdmax, rng) if edges == "random" else \
+                        edge_pattern(edges + ("", "_odd")[(bits + k) & 1], bt.bdmax)
+                    bt.add(mode, w, h, e, angle=a | (bits << 9), max_w=mw, max_h=mh)
+    assert len(bt.recs) >= 54 * 19 * 4
+    bt.run(gpu)
+
+
+@pytest.mark.parametrize("bpc", [8, 10, 12])
+def test_ipred_extreme_edges(gpu, bpc):
+    """DC and its three fallbacks (the rectangular multiply at 12 bits with every sample at
+    bdmax), V, H, the SMOOTH modes, PAETH at every size, and the five filter-intra filters up
+    to 32x32, over edges of all 0, all bdmax, alternating (both phases), top against left at
+    opposite extremes (both ways) and a full-range ramp: the sums at both clips."""
+    bt = Batch(bpc)
+    for name in EXTREME_PATTERNS:
+        e = edge_pattern(name, bt.bdmax)
+        for w, h in SIZES:
+            for mode in (0, 3, 4, 5, 1, 2, 9, 10, 11, 12):
+                bt.add(mode, w, h, e)
+            if w <= 32 and h <= 32:
+                for filt in range(5):
+                    bt.add(13, w, h, e, angle=filt)
+    bt.run(gpu)
+
+
+@pytest.mark.parametrize("bpc", [8, 10, 12])
+def test_ipred_extreme_cfl_and_palette(gpu, bpc):
+    """CfL on its four DC slots with alpha at both ends and at +-1, the AC all +(bdmax << 3),
+    all -(bdmax << 3) and a checkerboard of the two, over all-0 and all-bdmax edges (alpha * ac
+    far past the pixel range on both sides); palettes of {0, bdmax} with indices all 0, all 7
+    and alternating."""
+    bt = Batch(bpc)
+    lim = bt.bdmax << 3
+    for w, h in SIZES:
+        yy, xx = np.mgrid[0:h, 0:w]
+        board = np.where((yy + xx) & 1, lim, -lim)
+        for slot in (0, 3, 4, 5):
+            for alpha in (-16, -1, 1, 16):
+                for ac in (np.full((h, w), lim), np.full((h, w), -lim), board):
+                    for name in ("zero", "max"):
+                        bt.add(IPRED_CFL + slot, w, h, edge_pattern(name, bt.bdmax), ac=ac, alpha=alpha)
+        for first in (0, bt.bdmax):
+            pal = edge_pattern("zero", bt.bdmax)
+            pal[130:138] = [first, bt.bdmax - first] * 4       # (the palette sits at edge_off)
+            for idx in (np.zeros((h, w)), np.full((h, w), 7), (yy + xx) & 1, 6 + ((yy + xx) & 1)):
+                bt.add(IPRED_PAL, w, h, pal, idx=idx)
+    bt.run(gpu)
