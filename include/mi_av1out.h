@@ -300,6 +300,64 @@ typedef struct MiScaledImage {
 int mi_display_scaled(MiCtx *ctx, const MiPicture *in, const MiScaledImage *outs, int n_outs,
                       const MiColorInfo *color, const MiFilmGrainData *fg, void *stream);
 
+/* ---- resampling filters of the tensor and scaled outputs (librav1d_amd.so) ---------------- */
+
+/* The filter of the resize of mi_display_tensor and mi_display_scaled: the triangle written there,
+ * or a Mitchell-Netravali cubic (B, C) of radius 2, widened by the downscale ratio like the
+ * triangle: (0, 0.5) is Catmull-Rom (Keys a = -0.5: PIL, torch with antialiasing), (0, 0.75) Keys
+ * a = -0.75 (OpenCV, torch without antialiasing), (0, 0.6) swscale's default bicubic, (1/3, 1/3)
+ * Mitchell. One filter applies to every rung and every plane of a call.
+ *
+ * MI_RS_CUBIC replaces the resize step of those definitions; crop, sitings, finish, depth and
+ * stores stay. Per axis (n_in the crop extent, n_out the output extent, S = 18, P the phase: 2 on a
+ * centred axis, 4 on a co-sited one, chosen as written at mi_display_scaled):
+ *   n_in == n_out is the identity for every filter: start = o, one tap of 2^S (so B > 0 does not
+ *   blur an axis that is not resized). Otherwise, in exact integers, Rr = P max(n_in, n_out),
+ *   C = (P o + 1) n_in, d_i = |C - (P i + 1) n_out|; the taps are every i with d_i < 2 Rr (at most
+ *   4 ceil(max(n_in, n_out) / n_out) + 1 of them); tap i reads crop sample clamp(i, 0, n_in - 1).
+ *   Weights, in float64, every operation rounded on its own in the order written (no fused
+ *   multiply-add), b and c the float32 members widened to double: t = d_i / Rr,
+ *     w_i = ((p3 t + p2) t + p1) t + p0, with
+ *     d_i < Rr:  p3 = 12 - 9 b - 6 c, p2 = -18 + 12 b + 6 c, p1 = 0, p0 = 6 - 2 b;
+ *     otherwise: p3 = -b - 6 c, p2 = 6 b + 30 c, p1 = -12 b - 48 c, p0 = 8 b + 24 c
+ *   (each coefficient evaluated left to right: (12 - 9 b) - 6 c, ((-18) + 12 b) + 6 c, (-b) - 6 c, ...;
+ *   six times the usual kernel: the normalisation removes the factor).
+ *   W = the sum of the w_i in ascending i; k_i = floor(w_i / W * 2^S + 0.5) (the quotient first);
+ *   2^S - sum k_i is added to the first tap with the largest w_i. A weight that is zero inside the
+ *   support stays a tap; slots j >= count hold zero.
+ *   Each pass: out[o] = clamp((sum k_i x_i + 2^(S-1)) >> S, 0, M), an arithmetic shift of the
+ *   signed sum, M = 2^depth - 1 of the samples the pass runs over (Ms for the scaled planes, the
+ *   tone-mapped depth for a tensor with `tm`). The horizontal pass's clamped integer is what the
+ *   vertical pass reads. sum |k_i| <= 1.54 * 2^S for every (b, c) in [0, 1]^2 and every size the
+ *   64:1 limit admits, so 32-bit sums hold at 12 bits. */
+enum { MI_RS_TRIANGLE = 0, MI_RS_CUBIC = 1 };
+typedef struct MiResample { int32_t filter; float b, c; } MiResample;   /* b, c: Mitchell-Netravali, read for MI_RS_CUBIC only */
+
+/* mi_display_tensor (tm NULL: no colour-volume stage) or mi_display_tensor_tm with the filter
+ * `rs`. rs == NULL or MI_RS_TRIANGLE is exactly that call: the same kernels, the same output bit
+ * for bit. Their checks apply; in addition -EINVAL for a filter outside the list and, for
+ * MI_RS_CUBIC, a b or c that is not finite or lies outside [0, 1]. Every check precedes any device
+ * work, the NULL `ctx` last. The 64:1 limit stays. The context's tap tables are reused only by a
+ * call with the same geometry and the same filter, b and c. */
+int mi_display_tensor_rs(MiCtx *ctx, const MiPicture *in, const MiTensorImage *out, const MiColorInfo *color,
+                         const MiToneMap *tm, const MiResample *rs, const MiFilmGrainData *fg, void *stream);
+/* mi_display_scaled with the filter `rs`, by the same rules. */
+int mi_display_scaled_rs(MiCtx *ctx, const MiPicture *in, const MiScaledImage *outs, int n_outs,
+                         const MiColorInfo *color, const MiResample *rs, const MiFilmGrainData *fg, void *stream);
+
+/* Host only, no device and no context: the sizes the device passes use for an axis n_in -> n_out
+ * under `rs` (NULL: the triangle). *cap: the slots per output of its tap table; *seg_outputs: the
+ * output columns one workgroup of the horizontal pass takes, sized so that the source columns their
+ * taps reach, with the 15 the 8-column runs of the tile spend, fit 2048. -EINVAL for a NULL `cap`
+ * or `seg_outputs`, a bad `rs`, n_in or n_out outside 1..65536, n_in > 64 n_out. */
+int mi_resample_plan(const MiResample *rs, int n_in, int n_out, int *cap, int *seg_outputs);
+/* Host only: the tap table of the axis, from the source the device's table kernel runs: output o
+ * reads crop sample clamp(start[o] + j, 0, n_in - 1) with weight k[j * n_out + o], j < count[o];
+ * slots count[o] <= j < cap hold zero. phase: 2 centred, 4 co-sited. -EINVAL as mi_resample_plan,
+ * for a NULL table, a phase other than 2 and 4, and a `cap` below mi_resample_plan's. */
+int mi_resample_taps(const MiResample *rs, int n_in, int n_out, int phase, int cap,
+                     int32_t *start, int32_t *count, int32_t *k /* [cap][n_out] */);
+
 #ifdef __cplusplus
 }
 #endif

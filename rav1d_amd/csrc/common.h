@@ -525,12 +525,15 @@ template <bool TM> using ToneParam = typename ToneSel<TM>::type;
 // RGB formats only; the destination samples are u8 at dst_bpc 8, else u16
 int launch_display_tm(const DisplayArgs &a, const ToneArgs &tm, int bpc, int dst_bpc, int format, hipStream_t s);
 
-// the separable triangle resize of the tensor and scaled outputs (resize.h): one axis of a tap
-// table, and the list of axes one launch of the taps kernel fills (a scaled call: up to 8 rungs of
-// luma x, luma y, chroma x, chroma y)
+// the separable resize of the tensor and scaled outputs (resize.h): one axis of a tap table, and
+// the list of axes one launch of the taps kernel fills (a scaled call: up to 8 rungs of luma x,
+// luma y, chroma x, chroma y)
 constexpr int kTapAxes = 32;
 struct TapAxis { int n_in, n_out, phase, cap; int *tab; };   // phase 2: centred, 4: co-sited
-struct TapList { TapAxis ax[kTapAxes]; int n; };
+// One filter for every axis of a call: MI_RS_* and, for MI_RS_CUBIC, the Mitchell-Netravali b and c
+// (zero for the triangle). They follow the axes, which lie where they did when the triangle was
+// the only filter: its table kernel reads the same kernel arguments as then.
+struct TapList { TapAxis ax[kTapAxes]; int n; int filter; float b, c; };
 
 // tensor output (tensor.hip): crop, separable triangle resize (resize.h), finish to
 // u8 / f16 / bf16 / f32, of the R'G'B' picture DisplayArgs `d` describes (its source half only).
@@ -553,8 +556,9 @@ struct TensorArgs {
 };
 enum { kTensorCHW = 0, kTensorHWC = 1, kTensorAny = 2 };
 // the two passes (the tap tables are in place); tm: the colour-volume stage in the tile fill of
-// the horizontal pass, or nullptr
-int launch_tensor(const TensorArgs &t, int bpc, int order, hipStream_t s, const ToneArgs *tm = nullptr);
+// the horizontal pass, or nullptr; cubic: the tables hold signed taps (MI_RS_CUBIC) and the passes
+// clamp their sums to [0, (256 << shift) - 1]
+int launch_tensor(const TensorArgs &t, int bpc, int order, hipStream_t s, const ToneArgs *tm = nullptr, bool cubic = false);
 
 // scaled semi-planar output (scaled.hip): per rung, the luma plane and the U / V pair each cropped,
 // resized (resize.h, with the chroma siting in the taps), converted to the rung's depth and stored
@@ -583,7 +587,10 @@ struct ScaledArgs {
     int up;                       // left shift after it: (d - s when d > s) + (16 - d when d > 8)
     int maxd;                     // Md
 };
-int launch_scaled(const ScaledArgs &a, int src_bpc, int dst_bpc, hipStream_t s);
+// MI_RS_CUBIC: the passes clamp their signed sums to [0, maxs] (Ms). A struct of its own, so that
+// the triangle's kernels keep the arguments, and with them the code, they had
+struct ScaledCubicArgs : ScaledArgs { int maxs; };
+int launch_scaled(const ScaledArgs &a, int src_bpc, int dst_bpc, hipStream_t s, bool cubic = false);
 
 // ---- per-call (table-compatible) entry points: single-block kernels ----
 struct LfCallArgs {

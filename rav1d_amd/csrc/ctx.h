@@ -14,8 +14,11 @@
 struct MiResizeScratch {
     uint8_t *p = nullptr;
     size_t bytes = 0;
-    // the axis count, then n_in, n_out, phase per axis of the tables held (all 0: none)
-    int key[1 + 3 * mi::kTapAxes] = {0};
+    // the axis count, the filter and the bits of its b and c, then n_in, n_out, phase per axis of
+    // the tables held (all 0: none): another filter on the same geometry has other tables, and
+    // other capacities too
+    static constexpr int kKeyHead = 4;
+    int key[kKeyHead + 3 * mi::kTapAxes] = {0};
     // Before any launch of the call: at least `need` bytes, or false with nothing held. Growing
     // loses the tables.
     bool ensure(size_t need) {
@@ -29,7 +32,7 @@ struct MiResizeScratch {
         return true;
     }
     bool holds(const mi::TapList &t) const {
-        int k[1 + 3 * mi::kTapAxes];
+        int k[kKeyHead + 3 * mi::kTapAxes];
         fill(t, k);
         return memcmp(k, key, sizeof(key)) == 0;
     }
@@ -42,7 +45,13 @@ struct MiResizeScratch {
     static void fill(const mi::TapList &t, int *k) {
         memset(k, 0, sizeof(key));
         k[0] = t.n;
-        for (int a = 0; a < t.n; a++) k[1 + 3 * a] = t.ax[a].n_in, k[2 + 3 * a] = t.ax[a].n_out, k[3 + 3 * a] = t.ax[a].phase;
+        k[1] = t.filter;
+        memcpy(k + 2, &t.b, sizeof(float));
+        memcpy(k + 3, &t.c, sizeof(float));
+        for (int a = 0; a < t.n; a++) {
+            int *q = k + kKeyHead + 3 * a;
+            q[0] = t.ax[a].n_in, q[1] = t.ax[a].n_out, q[2] = t.ax[a].phase;
+        }
     }
 };
 

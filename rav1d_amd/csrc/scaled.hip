@@ -1,6 +1,8 @@
 // scaled.hip — mi_display_scaled (include/mi_av1out.h): a shown picture as cropped, resized
 // semi-planar YUV at a chosen depth, up to 8 rungs of a transcode ladder per call. The resize is
-// the separable 18-bit triangle filter of resize.h run in the YUV domain: every plane on its own,
+// the separable 18-bit filter of resize.h (the triangle, or with mi_display_scaled_rs a cubic: its
+// signed sums are clamped to [0, Ms] by CUBIC, a compile-time switch of both passes that leaves
+// the triangle's instantiations as they were) run in the YUV domain: every plane on its own,
 // at its own resolution, the chroma siting in the taps (a co-sited axis takes the (4o+1) / (4i+1)
 // form of the formula), so there is no chroma upsample and no matrix.
 //
@@ -32,8 +34,8 @@ namespace mi {
 namespace {
 
 // ---- horizontal pass ----
-template <typename Px, int NC>
-__device__ __forceinline__ void h_pass(const ScaledPlane &p, int r, int seg, uint16_t (&tile)[2][kTensorSeg]) {
+template <typename Px, int NC, bool CUBIC>
+__device__ __forceinline__ void h_pass(const ScaledPlane &p, int r, int seg, uint16_t (&tile)[2][kTensorSeg], [[maybe_unused]] int maxs) {
     const int o0 = seg * p.ob, o1 = min(o0 + p.ob, p.ow) - 1;
     const int *hs = p.htab, *hc = hs + p.ow, *hk = hc + p.ow;
     // plane columns [lo, hi) the segment's taps read, inside the crop whatever the tables hold;
@@ -60,25 +62,39 @@ __device__ __forceinline__ void h_pass(const ScaledPlane &p, int r, int seg, uin
 #pragma unroll 4
         for (int j = 0; j < p.th; j++) h_tap<NC>(tile, base + j, lo_i, hi_i, k[(int64_t)j * p.ow], acc);
 #pragma unroll
-        for (int c = 0; c < NC; c++)
-            p.mid[((int64_t)c * p.pch + r) * p.mstride + o] = (uint16_t)(acc[c] >> kTensorS);
+        for (int c = 0; c < NC; c++) {
+            int v = acc[c] >> kTensorS;
+            if constexpr (CUBIC) v = min(max(v, 0), maxs);
+            p.mid[((int64_t)c * p.pch + r) * p.mstride + o] = (uint16_t)v;
+        }
     }
 }
 
-template <typename Px>
-__global__ __launch_bounds__(256) void scaled_h_kernel(const ScaledArgs a) {
+template <bool CUBIC> struct ScaledSel { using type = ScaledArgs; };
+template <> struct ScaledSel<true> { using type = ScaledCubicArgs; };
+template <bool CUBIC> using ScaledParam = typename ScaledSel<CUBIC>::type;
+template <bool CUBIC>
+__device__ __forceinline__ int clamp_max(const ScaledParam<CUBIC> &a) {
+    if constexpr (CUBIC)
+        return a.maxs;
+    else
+        return 0;   // (not read)
+}
+
+template <typename Px, bool CUBIC>
+__global__ __launch_bounds__(256) void scaled_h_kernel(const ScaledParam<CUBIC> a) {
     __shared__ __attribute__((aligned(16))) uint16_t tile[2][kTensorSeg];
     const int r = blockIdx.x, seg = blockIdx.y;
     if (r < a.p[0].pch) {   // (block-uniform: every lane of a workgroup meets the barrier or none)
-        if (seg < a.p[0].segs) h_pass<Px, 1>(a.p[0], r, seg, tile);
+        if (seg < a.p[0].segs) h_pass<Px, 1, CUBIC>(a.p[0], r, seg, tile, clamp_max<CUBIC>(a));
     } else if (a.nplanes > 1 && r - a.p[0].pch < a.p[1].pch) {
-        if (seg < a.p[1].segs) h_pass<Px, 2>(a.p[1], r - a.p[0].pch, seg, tile);
+        if (seg < a.p[1].segs) h_pass<Px, 2, CUBIC>(a.p[1], r - a.p[0].pch, seg, tile, clamp_max<CUBIC>(a));
     }
 }
 
 // ---- vertical pass, depth, store ----
-template <typename Dx, int NC>
-__device__ __forceinline__ void v_pass(const ScaledArgs &a, const ScaledPlane &p, int oy, int xb) {
+template <typename Dx, int NC, bool CUBIC>
+__device__ __forceinline__ void v_pass(const ScaledArgs &a, const ScaledPlane &p, int oy, int xb, [[maybe_unused]] int maxs) {
     const int x0 = (xb * 256 + (int)threadIdx.x) * 4;
     if (x0 >= p.ow) return;
     const int *vs = p.vtab, *vk = vs + 2 * p.oh;
@@ -101,6 +117,7 @@ __device__ __forceinline__ void v_pass(const ScaledArgs &a, const ScaledPlane &p
 #pragma unroll
         for (int i = 0; i < 4; i++) {
             int v = acc[c][i] >> kTensorS;
+            if constexpr (CUBIC) v = min(max(v, 0), maxs);
             if (a.down) v = min(a.maxd, (v + (1 << (a.down - 1))) >> a.down);
             e[NC * i + c] = (uint32_t)(v << a.up);
         }
@@ -126,34 +143,42 @@ __device__ __forceinline__ void v_pass(const ScaledArgs &a, const ScaledPlane &p
     }
 }
 
-template <typename Dx>
-__global__ __launch_bounds__(256) void scaled_v_kernel(const ScaledArgs a) {
+template <typename Dx, bool CUBIC>
+__global__ __launch_bounds__(256) void scaled_v_kernel(const ScaledParam<CUBIC> a) {
     const int n0 = a.p[0].xblocks * a.p[0].oh;
     int b = blockIdx.x;
     if (b < n0) {
-        v_pass<Dx, 1>(a, a.p[0], b / a.p[0].xblocks, b % a.p[0].xblocks);
+        v_pass<Dx, 1, CUBIC>(a, a.p[0], b / a.p[0].xblocks, b % a.p[0].xblocks, clamp_max<CUBIC>(a));
     } else if (a.nplanes > 1) {
         b -= n0;
-        if (b < a.p[1].xblocks * a.p[1].oh) v_pass<Dx, 2>(a, a.p[1], b / a.p[1].xblocks, b % a.p[1].xblocks);
+        if (b < a.p[1].xblocks * a.p[1].oh) v_pass<Dx, 2, CUBIC>(a, a.p[1], b / a.p[1].xblocks, b % a.p[1].xblocks, clamp_max<CUBIC>(a));
     }
+}
+
+template <bool CUBIC>
+int launch_passes(const ScaledArgs &args, int src_bpc, int dst_bpc, hipStream_t s) {
+    ScaledParam<CUBIC> a;
+    static_cast<ScaledArgs &>(a) = args;
+    if constexpr (CUBIC) a.maxs = (1 << src_bpc) - 1;
+    const bool chroma = a.nplanes > 1;
+    const dim3 hgrid(a.p[0].pch + (chroma ? a.p[1].pch : 0), chroma ? std::max(a.p[0].segs, a.p[1].segs) : a.p[0].segs);
+    if (src_bpc == 8)
+        scaled_h_kernel<uint8_t, CUBIC><<<hgrid, 256, 0, s>>>(a);
+    else
+        scaled_h_kernel<uint16_t, CUBIC><<<hgrid, 256, 0, s>>>(a);
+    if (hipGetLastError() != hipSuccess) return -1;
+    const unsigned vgrid = (unsigned)a.p[0].xblocks * (unsigned)a.p[0].oh + (chroma ? (unsigned)a.p[1].xblocks * (unsigned)a.p[1].oh : 0u);
+    if (dst_bpc == 8)
+        scaled_v_kernel<uint8_t, CUBIC><<<vgrid, 256, 0, s>>>(a);
+    else
+        scaled_v_kernel<uint16_t, CUBIC><<<vgrid, 256, 0, s>>>(a);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
 }  // namespace
 
-int launch_scaled(const ScaledArgs &a, int src_bpc, int dst_bpc, hipStream_t s) {
-    const bool chroma = a.nplanes > 1;
-    const dim3 hgrid(a.p[0].pch + (chroma ? a.p[1].pch : 0), chroma ? std::max(a.p[0].segs, a.p[1].segs) : a.p[0].segs);
-    if (src_bpc == 8)
-        scaled_h_kernel<uint8_t><<<hgrid, 256, 0, s>>>(a);
-    else
-        scaled_h_kernel<uint16_t><<<hgrid, 256, 0, s>>>(a);
-    if (hipGetLastError() != hipSuccess) return -1;
-    const unsigned vgrid = (unsigned)a.p[0].xblocks * (unsigned)a.p[0].oh + (chroma ? (unsigned)a.p[1].xblocks * (unsigned)a.p[1].oh : 0u);
-    if (dst_bpc == 8)
-        scaled_v_kernel<uint8_t><<<vgrid, 256, 0, s>>>(a);
-    else
-        scaled_v_kernel<uint16_t><<<vgrid, 256, 0, s>>>(a);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+int launch_scaled(const ScaledArgs &a, int src_bpc, int dst_bpc, hipStream_t s, bool cubic) {
+    return cubic ? launch_passes<true>(a, src_bpc, dst_bpc, s) : launch_passes<false>(a, src_bpc, dst_bpc, s);
 }
 
 }  // namespace mi
@@ -168,10 +193,9 @@ struct PlaneGeom {
     size_t htab, vtab, mid;   // byte offsets
 };
 
-}  // namespace
-
-extern "C" int mi_display_scaled(MiCtx *ctx, const MiPicture *in, const MiScaledImage *outs, int n_outs,
-                                 const MiColorInfo *color, const MiFilmGrainData *fg, void *stream) {
+// mi_display_scaled (rs NULL) and mi_display_scaled_rs
+int display_scaled(MiCtx *ctx, const MiPicture *in, const MiScaledImage *outs, int n_outs, const MiColorInfo *color,
+                   const MiResample *rs, const MiFilmGrainData *fg, void *stream) {
     if (!in || !outs || n_outs < 1 || n_outs > 8) return -EINVAL;
     if (int e = mi::display_check_picture(in)) return e;
     if (int e = mi::display_check_strides(in)) return e;
@@ -205,6 +229,9 @@ extern "C" int mi_display_scaled(MiCtx *ctx, const MiPicture *in, const MiScaled
     }
     const int chr = color ? color->chr : 0;
     if (chr < 0 || chr > 2) return -EINVAL;
+    mi::Filter flt;
+    if (int e = mi::resample_check(rs, flt)) return e;
+    const int radius = mi::filter_radius(flt);
     if (!ctx) return -EINVAL;
 
     // the scratch: every rung's tables (they stay while the axes stay), then one `mid` the rungs
@@ -215,8 +242,8 @@ extern "C" int mi_display_scaled(MiCtx *ctx, const MiPicture *in, const MiScaled
         size_t mid = 0;
         for (int p = 0; p < nplanes; p++) {
             PlaneGeom &q = g[r][p];
-            q.th = mi::tap_cap(q.pcw, q.ow);
-            q.tv = mi::tap_cap(q.pch, q.oh);
+            q.th = mi::tap_cap(q.pcw, q.ow, radius);
+            q.tv = mi::tap_cap(q.pch, q.oh, radius);
             q.mstride = ((int64_t)q.ow + 7) & ~(int64_t)7;
             q.htab = tab_bytes;
             tab_bytes += (size_t)(q.th + 2) * q.ow * sizeof(int);
@@ -240,6 +267,7 @@ extern "C" int mi_display_scaled(MiCtx *ctx, const MiPicture *in, const MiScaled
             tl.ax[tl.n++] = mi::TapAxis{q.pcw, q.ow, q.phx, q.th, (int *)(sc.p + q.htab)};
             tl.ax[tl.n++] = mi::TapAxis{q.pch, q.oh, q.phy, q.tv, (int *)(sc.p + q.vtab)};
         }
+    mi::tap_filter(tl, flt);
     const bool taps = !sc.holds(tl);
     MiPicture src = *in;
     if (fg)
@@ -271,15 +299,27 @@ extern "C" int mi_display_scaled(MiCtx *ctx, const MiPicture *in, const MiScaled
             sp.th = q.th, sp.tv = q.tv;
             sp.mid = (uint16_t *)(sc.p + tab_bytes + q.mid);
             sp.mstride = q.mstride;
-            sp.ob = mi::seg_outputs(q.pcw, q.ow);
+            sp.ob = mi::seg_outputs(q.pcw, q.ow, radius);
             sp.segs = (q.ow + sp.ob - 1) / sp.ob;
             sp.xblocks = (q.ow + 1023) / 1024;
             sp.dst = (uint8_t *)o.data[p];
             sp.dstride = o.stride[p];
             sp.dvec = mi::aligned_to(o.data[p], o.stride[p], (p ? 8 : 4) * es);
         }
-        if (mi::launch_scaled(a, in->bpc, o.bpc, (hipStream_t)stream)) return ctx->last_error = -EIO;
+        if (mi::launch_scaled(a, in->bpc, o.bpc, (hipStream_t)stream, flt.filter == MI_RS_CUBIC)) return ctx->last_error = -EIO;
     }
     sc.keep(tl);
     return 0;
+}
+
+}  // namespace
+
+extern "C" int mi_display_scaled(MiCtx *ctx, const MiPicture *in, const MiScaledImage *outs, int n_outs,
+                                 const MiColorInfo *color, const MiFilmGrainData *fg, void *stream) {
+    return display_scaled(ctx, in, outs, n_outs, color, nullptr, fg, stream);
+}
+
+extern "C" int mi_display_scaled_rs(MiCtx *ctx, const MiPicture *in, const MiScaledImage *outs, int n_outs,
+                                    const MiColorInfo *color, const MiResample *rs, const MiFilmGrainData *fg, void *stream) {
+    return display_scaled(ctx, in, outs, n_outs, color, rs, fg, stream);
 }

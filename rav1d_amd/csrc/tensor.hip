@@ -1,8 +1,8 @@
 // tensor.hip — mi_display_tensor (include/mi_av1out.h): a shown picture as the cropped, resized,
 // normalised R'G'B' tensor an ML consumer on the device reads, in one pass over the decoded planes.
 // The picture is the one MI_OUT_RGB_PLANAR gives (display.h: the same loads, chroma upsampler and
-// matrix); the resize is the separable 18-bit triangle filter of resize.h, both axes centred,
-// horizontal pass first.
+// matrix); the resize is the separable 18-bit filter of resize.h (the triangle, or with
+// mi_display_tensor_rs a cubic), both axes centred, horizontal pass first.
 //
 // Three launches on the caller's stream, all scratch in one context-owned allocation:
 //   taps_kernel          (resize.h) the tap tables of the two axes; skipped when the context's
@@ -22,6 +22,8 @@
 //
 // mi_display_tensor_tm: the colour-volume stage (display.h tone_run) runs in the tile fill of
 // tensor_h_kernel, a compile-time switch, so the passes resize the tone-mapped picture at dst_bpc.
+// A cubic's taps are signed: CUBIC, a compile-time switch of both passes, clamps what the shift
+// gives to [0, M]; the triangle's instantiations are the code they were without it.
 #include <algorithm>
 #include <cerrno>
 #include <cmath>
@@ -48,7 +50,7 @@ __device__ __forceinline__ void tile_row(const DisplayArgs &a, const ToneParam<T
 }
 
 // ---- horizontal pass ----
-template <typename Px, bool TM>
+template <typename Px, bool TM, bool CUBIC>
 __global__ __launch_bounds__(256) void tensor_h_kernel(const TensorArgs t, const ToneParam<TM> tm) {
     __shared__ __attribute__((aligned(16))) uint16_t tile[2][3][kTensorSeg];
     [[maybe_unused]] const float *lin = nullptr;
@@ -91,7 +93,11 @@ __global__ __launch_bounds__(256) void tensor_h_kernel(const TensorArgs t, const
         for (int j = 0; j < t.th; j++) h_tap<3>(tile[r], base + j, lo_i, hi_i, k[(int64_t)j * t.ow], acc);
         uint16_t *m = t.mid + (int64_t)(r0 + r - t.cy) * t.mstride + o;
 #pragma unroll
-        for (int c = 0; c < 3; c++) m[(int64_t)c * t.ch * t.mstride] = (uint16_t)(acc[c] >> kTensorS);
+        for (int c = 0; c < 3; c++) {
+            int v = acc[c] >> kTensorS;
+            if constexpr (CUBIC) v = min(max(v, 0), (256 << t.shift) - 1);
+            m[(int64_t)c * t.ch * t.mstride] = (uint16_t)v;
+        }
     }
 }
 
@@ -137,7 +143,7 @@ __device__ __forceinline__ void store4(uint8_t *p, const E (&e)[4]) {
         *reinterpret_cast<uint4 *>(p) = make_uint4(e[0], e[1], e[2], e[3]);
 }
 
-template <int DT, int ORDER>
+template <int DT, int ORDER, bool CUBIC>
 __global__ __launch_bounds__(256) void tensor_v_kernel(const TensorArgs t) {
     using E = typename Elem<DT>::type;
     const int xb = blockIdx.x % t.xblocks, oy = blockIdx.x / t.xblocks;
@@ -160,7 +166,11 @@ __global__ __launch_bounds__(256) void tensor_v_kernel(const TensorArgs t) {
 #pragma unroll
     for (int c = 0; c < 3; c++)
 #pragma unroll
-        for (int i = 0; i < 4; i++) e[c][i] = finish<DT>(t, acc[c][i] >> kTensorS, c);
+        for (int i = 0; i < 4; i++) {
+            int v = acc[c][i] >> kTensorS;
+            if constexpr (CUBIC) v = min(max(v, 0), (256 << t.shift) - 1);
+            e[c][i] = finish<DT>(t, v, c);
+        }
     const bool whole = t.vec && x0 + 4 <= t.ow;
     uint8_t *drow = t.dst + oy * t.dstride[1];
     if constexpr (ORDER == kTensorCHW) {
@@ -202,47 +212,53 @@ __global__ __launch_bounds__(256) void tensor_v_kernel(const TensorArgs t) {
     }
 }
 
-template <int DT>
+template <int DT, bool CUBIC>
 void launch_v(const TensorArgs &t, int order, dim3 grid, hipStream_t s) {
     switch (order) {
-    case kTensorCHW: tensor_v_kernel<DT, kTensorCHW><<<grid, 256, 0, s>>>(t); break;
-    case kTensorHWC: tensor_v_kernel<DT, kTensorHWC><<<grid, 256, 0, s>>>(t); break;
-    default: tensor_v_kernel<DT, kTensorAny><<<grid, 256, 0, s>>>(t); break;
+    case kTensorCHW: tensor_v_kernel<DT, kTensorCHW, CUBIC><<<grid, 256, 0, s>>>(t); break;
+    case kTensorHWC: tensor_v_kernel<DT, kTensorHWC, CUBIC><<<grid, 256, 0, s>>>(t); break;
+    default: tensor_v_kernel<DT, kTensorAny, CUBIC><<<grid, 256, 0, s>>>(t); break;
     }
 }
 
-}  // namespace
-
-int launch_tensor(const TensorArgs &t, int bpc, int order, hipStream_t s, const ToneArgs *tm) {
+template <bool CUBIC>
+int launch_passes(const TensorArgs &t, int bpc, int order, hipStream_t s, const ToneArgs *tm) {
     const dim3 hgrid(t.units, t.segs);
     if (tm) {
         if (bpc == 8)
-            tensor_h_kernel<uint8_t, true><<<hgrid, 256, 0, s>>>(t, *tm);
+            tensor_h_kernel<uint8_t, true, CUBIC><<<hgrid, 256, 0, s>>>(t, *tm);
         else
-            tensor_h_kernel<uint16_t, true><<<hgrid, 256, 0, s>>>(t, *tm);
+            tensor_h_kernel<uint16_t, true, CUBIC><<<hgrid, 256, 0, s>>>(t, *tm);
     } else if (bpc == 8) {
-        tensor_h_kernel<uint8_t, false><<<hgrid, 256, 0, s>>>(t, NoTone());
+        tensor_h_kernel<uint8_t, false, CUBIC><<<hgrid, 256, 0, s>>>(t, NoTone());
     } else {
-        tensor_h_kernel<uint16_t, false><<<hgrid, 256, 0, s>>>(t, NoTone());
+        tensor_h_kernel<uint16_t, false, CUBIC><<<hgrid, 256, 0, s>>>(t, NoTone());
     }
     if (hipGetLastError() != hipSuccess) return -1;
     const dim3 vgrid((unsigned)t.xblocks * (unsigned)t.oh);
     switch (t.dtype) {
-    case MI_T_U8: launch_v<MI_T_U8>(t, order, vgrid, s); break;
-    case MI_T_F16: launch_v<MI_T_F16>(t, order, vgrid, s); break;
-    case MI_T_BF16: launch_v<MI_T_BF16>(t, order, vgrid, s); break;
-    default: launch_v<MI_T_F32>(t, order, vgrid, s); break;
+    case MI_T_U8: launch_v<MI_T_U8, CUBIC>(t, order, vgrid, s); break;
+    case MI_T_F16: launch_v<MI_T_F16, CUBIC>(t, order, vgrid, s); break;
+    case MI_T_BF16: launch_v<MI_T_BF16, CUBIC>(t, order, vgrid, s); break;
+    default: launch_v<MI_T_F32, CUBIC>(t, order, vgrid, s); break;
     }
     return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+}  // namespace
+
+int launch_tensor(const TensorArgs &t, int bpc, int order, hipStream_t s, const ToneArgs *tm, bool cubic) {
+    return cubic ? launch_passes<true>(t, bpc, order, s, tm) : launch_passes<false>(t, bpc, order, s, tm);
 }
 
 }  // namespace mi
 
 namespace {
 
-// mi_display_tensor (tone false; tm not read) and mi_display_tensor_tm (tone true)
+// mi_display_tensor (tone false; tm not read), mi_display_tensor_tm (tone true) and, with a
+// filter, mi_display_tensor_rs
 int display_tensor(MiCtx *ctx, const MiPicture *in, const MiTensorImage *out, const MiColorInfo *color, bool tone,
-                   const MiToneMap *tm, const MiFilmGrainData *fg, void *stream) {
+                   const MiToneMap *tm, const MiResample *rs, const MiFilmGrainData *fg, void *stream) {
     if (!in || !out) return -EINVAL;
     if (int e = mi::display_check_picture(in)) return e;
     if (int e = mi::display_check_strides(in)) return e;
@@ -262,6 +278,9 @@ int display_tensor(MiCtx *ctx, const MiPicture *in, const MiTensorImage *out, co
         for (int c = 0; c < 3; c++)
             if (!std::isfinite(out->scale[c]) || !std::isfinite(out->bias[c])) return -EINVAL;
 
+    mi::Filter flt;
+    if (int e = mi::resample_check(rs, flt)) return e;
+
     mi::TensorArgs t;
     memset(&t, 0, sizeof(t));
     if (int e = mi::display_color(in, color, t.d)) return e;
@@ -272,10 +291,11 @@ int display_tensor(MiCtx *ctx, const MiPicture *in, const MiTensorImage *out, co
     // geometry of the passes and of the scratch
     const int ow = out->w, oh = out->h;
     t.cx = cx, t.cy = cy, t.cw = cw, t.ch = ch, t.ow = ow, t.oh = oh;
-    t.th = mi::tap_cap(cw, ow);
-    t.tv = mi::tap_cap(ch, oh);
+    const int radius = mi::filter_radius(flt);
+    t.th = mi::tap_cap(cw, ow, radius);
+    t.tv = mi::tap_cap(ch, oh, radius);
     t.mstride = ((int64_t)ow + 7) & ~(int64_t)7;
-    t.ob = mi::seg_outputs(cw, ow);
+    t.ob = mi::seg_outputs(cw, ow, radius);
     t.segs = (ow + t.ob - 1) / t.ob;
     t.u0 = cy >> ss_ver;
     t.units = ((cy + ch - 1) >> ss_ver) - t.u0 + 1;
@@ -292,6 +312,7 @@ int display_tensor(MiCtx *ctx, const MiPicture *in, const MiTensorImage *out, co
     memset(&tl, 0, sizeof(tl));
     tl.ax[tl.n++] = mi::TapAxis{cw, ow, 2, t.th, t.tab};
     tl.ax[tl.n++] = mi::TapAxis{ch, oh, 2, t.tv, t.tab + (int64_t)(t.th + 2) * ow};
+    mi::tap_filter(tl, flt);
     const bool taps = !sc.holds(tl);
     mi::ToneArgs ta;
     if (tone)
@@ -318,7 +339,7 @@ int display_tensor(MiCtx *ctx, const MiPicture *in, const MiTensorImage *out, co
     }
     sc.forget();
     if ((taps && mi::launch_taps(tl, (hipStream_t)stream)) ||
-        mi::launch_tensor(t, in->bpc, order, (hipStream_t)stream, tone ? &ta : nullptr))
+        mi::launch_tensor(t, in->bpc, order, (hipStream_t)stream, tone ? &ta : nullptr, flt.filter == MI_RS_CUBIC))
         return ctx->last_error = -EIO;
     sc.keep(tl);
     return 0;
@@ -328,10 +349,15 @@ int display_tensor(MiCtx *ctx, const MiPicture *in, const MiTensorImage *out, co
 
 extern "C" int mi_display_tensor(MiCtx *ctx, const MiPicture *in, const MiTensorImage *out, const MiColorInfo *color,
                                  const MiFilmGrainData *fg, void *stream) {
-    return display_tensor(ctx, in, out, color, false, nullptr, fg, stream);
+    return display_tensor(ctx, in, out, color, false, nullptr, nullptr, fg, stream);
 }
 
 extern "C" int mi_display_tensor_tm(MiCtx *ctx, const MiPicture *in, const MiTensorImage *out, const MiColorInfo *color,
                                     const MiToneMap *tm, const MiFilmGrainData *fg, void *stream) {
-    return display_tensor(ctx, in, out, color, true, tm, fg, stream);
+    return display_tensor(ctx, in, out, color, true, tm, nullptr, fg, stream);
+}
+
+extern "C" int mi_display_tensor_rs(MiCtx *ctx, const MiPicture *in, const MiTensorImage *out, const MiColorInfo *color,
+                                    const MiToneMap *tm, const MiResample *rs, const MiFilmGrainData *fg, void *stream) {
+    return display_tensor(ctx, in, out, color, tm != nullptr, tm, rs, fg, stream);
 }

@@ -6,7 +6,9 @@ cropped, resized, normalised R'G'B' tensor an ML consumer reads. With a ToneMap 
 colour-volume stage (mi_display_picture_tm / mi_display_tensor_tm: inverse transfer and, for PQ, the
 BT.2390 tone curve, primaries conversion, the destination's OETF at a chosen depth) in the same pass.
 display_scaled (mi_display_scaled, csrc/scaled.hip) writes cropped, resized semi-planar YUV at a
-chosen depth, several sizes per call: the rungs of a transcode ladder."""
+chosen depth, several sizes per call: the rungs of a transcode ladder. Both resize with the
+triangle filter, or with resample=Resample(...) (mi_display_tensor_rs / mi_display_scaled_rs) with a
+Mitchell-Netravali cubic: Catmull-Rom, Mitchell, Keys a = -0.75 or any (B, C) in [0, 1]^2."""
 import ctypes
 
 import numpy as np
@@ -133,6 +135,56 @@ def display_picture(ctx, frame, image, color=None, fg=None, stream=None, tonemap
           "mi_display_picture")
 
 
+RS_TRIANGLE, RS_CUBIC = 0, 1
+
+
+class MiResample(ctypes.Structure):
+    _fields_ = [("filter", ctypes.c_int32), ("b", ctypes.c_float), ("c", ctypes.c_float)]
+
+
+# named filters: (MI_RS_*, B, C)
+RESAMPLE_PRESETS = {"triangle": (RS_TRIANGLE, 0.0, 0.0), "catmull_rom": (RS_CUBIC, 0.0, 0.5),
+                    "mitchell": (RS_CUBIC, 1.0 / 3.0, 1.0 / 3.0), "cubic_075": (RS_CUBIC, 0.0, 0.75)}
+
+
+def Resample(filter="cubic", b=0.0, c=0.5):
+    """A MiResample: the filter of display_tensor's and display_scaled's resize. "cubic" takes the
+    Mitchell-Netravali (b, c), each in [0, 1] (the default is Catmull-Rom); the presets fix them:
+    "catmull_rom" (0, 0.5: Keys a = -0.5, what PIL and torch with antialiasing use), "mitchell"
+    (1/3, 1/3), "cubic_075" (0, 0.75: Keys a = -0.75, OpenCV and torch without antialiasing) and
+    "triangle", the filter of the calls without a MiResample."""
+    if filter == "cubic":
+        return MiResample(RS_CUBIC, float(b), float(c))
+    if filter not in RESAMPLE_PRESETS:
+        raise ValueError(f"filter {filter!r}: want 'cubic' or one of {sorted(RESAMPLE_PRESETS)}")
+    return MiResample(*RESAMPLE_PRESETS[filter])
+
+
+def resample_plan(rs, n_in, n_out):
+    """mi_resample_plan (host only): (cap, seg_outputs) of the axis n_in -> n_out under `rs` (a
+    MiResample, or None for the triangle): the slots per output of its tap table, and the output
+    columns one workgroup of the horizontal pass takes. Raises MiError on a negative return."""
+    cap, seg = ctypes.c_int(0), ctypes.c_int(0)
+    check(lib().mi_resample_plan(ctypes.byref(rs) if rs is not None else None, int(n_in), int(n_out),
+                                 ctypes.byref(cap), ctypes.byref(seg)), "mi_resample_plan")
+    return cap.value, seg.value
+
+
+def resample_taps(rs, n_in, n_out, phase=2):
+    """mi_resample_taps (host only): (start int32 [n_out], count int32 [n_out], k int32
+    [cap, n_out]), the tap table the device builds for the axis n_in -> n_out under `rs` (None: the
+    triangle) with phase 2 (centred) or 4 (co-sited): output o reads sample
+    clamp(start[o] + j, 0, n_in - 1) with weight k[j, o]. Raises MiError on a negative return."""
+    cap, _ = resample_plan(rs, n_in, n_out)
+    start = np.empty(n_out, dtype=np.int32)
+    count = np.empty(n_out, dtype=np.int32)
+    k = np.empty((cap, n_out), dtype=np.int32)
+    check(lib().mi_resample_taps(ctypes.byref(rs) if rs is not None else None, int(n_in), int(n_out), int(phase), cap,
+                                 start.ctypes.data_as(ctypes.c_void_p), count.ctypes.data_as(ctypes.c_void_p),
+                                 k.ctypes.data_as(ctypes.c_void_p)), "mi_resample_taps")
+    return start, count, k
+
+
 T_U8, T_F16, T_BF16, T_F32 = 0, 1, 2, 3
 _TENSOR_DTYPES = {torch.uint8: T_U8, torch.float16: T_F16, torch.bfloat16: T_BF16, torch.float32: T_F32}
 
@@ -174,7 +226,7 @@ def tensor_image(out, bpc, crop=None, mean=None, std=None, channels_last=False):
 
 
 def display_tensor(ctx, frame, out, color, fg=None, crop=None, mean=None, std=None, stream=None, channels_last=False,
-                   tonemap=None):
+                   tonemap=None, resample=None):
     """Enqueue mi_display_tensor: `frame` (a device Frame or a MiPicture) cropped to `crop`
     ((x, y, w, h) in luma pixels; None: the whole picture), resized to the size of `out` and
     normalised, as R'G'B' into `out`: a device tensor of shape (3, H, W) in any strides (batch[n] of
@@ -182,8 +234,9 @@ def display_tensor(ctx, frame, out, color, fg=None, crop=None, mean=None, std=No
     tensor's. Float dtypes receive (v / M - mean[c]) / std[c] (defaults 0 and 1: [0, 1]), uint8
     the sample at 8 bits. color: a MiColorInfo, as for display_picture's RGB formats; fg: film
     grain. `out` may also be a ready MiTensorImage. tonemap: a MiToneMap (ToneMap()): the call is
-    mi_display_tensor_tm, the resized picture is the tone-mapped one and M is 2^dst_bpc - 1. Raises
-    MiError on a negative return."""
+    mi_display_tensor_tm, the resized picture is the tone-mapped one and M is 2^dst_bpc - 1.
+    resample: a MiResample (Resample()): the call is mi_display_tensor_rs and the resize uses that
+    filter; None calls the entries without one (the triangle). Raises MiError on a negative return."""
     from .frame import _stream_ptr, film_grain_data
     src = frame if isinstance(frame, MiPicture) else frame.picture()
     bpc = src.bpc if tonemap is None else tonemap.dst_bpc
@@ -192,6 +245,11 @@ def display_tensor(ctx, frame, out, color, fg=None, crop=None, mean=None, std=No
         fg = film_grain_data(fg)
     cp = ctypes.byref(color) if color is not None else None
     fp = ctypes.byref(fg) if fg is not None else None
+    if resample is not None:
+        check(lib().mi_display_tensor_rs(ctx.h, ctypes.byref(src), ctypes.byref(im), cp,
+                                         ctypes.byref(tonemap) if tonemap is not None else None, ctypes.byref(resample),
+                                         fp, _stream_ptr(stream)), "mi_display_tensor_rs")
+        return
     if tonemap is not None:
         check(lib().mi_display_tensor_tm(ctx.h, ctypes.byref(src), ctypes.byref(im), cp, ctypes.byref(tonemap), fp,
                                          _stream_ptr(stream)), "mi_display_tensor_tm")
@@ -266,13 +324,15 @@ class ScaledImage:
         return out
 
 
-def display_scaled(ctx, frame, images, color=None, fg=None, stream=None):
+def display_scaled(ctx, frame, images, color=None, fg=None, stream=None, resample=None):
     """Enqueue mi_display_scaled: `frame` (a device Frame or a MiPicture) cropped, resized and
     converted to each rung's depth into `images`, 1 to 8 ScaledImage or MiScaledImage (or one of
     them on its own), semi-planar at the frame's own subsampling, in one call: film grain (`fg`: a
     MiFilmGrainData or a make_fg_params dict) is applied once and every rung reads the grained
     picture. color: a MiColorInfo or None; only its chr is read (the 4:2:0 chroma siting, of the
-    source and of the output). Raises MiError on a negative return."""
+    source and of the output). resample: a MiResample (Resample()): the call is
+    mi_display_scaled_rs and every plane of every rung is resized with that filter; None calls
+    mi_display_scaled (the triangle). Raises MiError on a negative return."""
     from .frame import _stream_ptr, film_grain_data
     src = frame if isinstance(frame, MiPicture) else frame.picture()
     if isinstance(images, (ScaledImage, MiScaledImage)):
@@ -282,9 +342,13 @@ def display_scaled(ctx, frame, images, color=None, fg=None, stream=None):
         ims[i] = image if isinstance(image, MiScaledImage) else image.image()
     if fg is not None and not isinstance(fg, MiFilmGrainData):
         fg = film_grain_data(fg)
-    check(lib().mi_display_scaled(ctx.h, ctypes.byref(src), ims, len(images),
-                                  ctypes.byref(color) if color is not None else None,
-                                  ctypes.byref(fg) if fg is not None else None, _stream_ptr(stream)),
+    cp = ctypes.byref(color) if color is not None else None
+    fp = ctypes.byref(fg) if fg is not None else None
+    if resample is not None:
+        check(lib().mi_display_scaled_rs(ctx.h, ctypes.byref(src), ims, len(images), cp, ctypes.byref(resample), fp,
+                                         _stream_ptr(stream)), "mi_display_scaled_rs")
+        return
+    check(lib().mi_display_scaled(ctx.h, ctypes.byref(src), ims, len(images), cp, fp, _stream_ptr(stream)),
           "mi_display_scaled")
 
 
@@ -292,4 +356,5 @@ __all__ = ["DisplayImage", "MiDisplayImage", "MiColorInfo", "display_picture", "
            "MiScaledImage", "ScaledImage", "display_scaled", "even_crop",
            "OUT_SEMIPLANAR", "OUT_RGB_PLANAR", "OUT_RGBA_PACKED",
            "MiTensorImage", "tensor_image", "display_tensor", "T_U8", "T_F16", "T_BF16", "T_F32",
-           "MiToneMap", "ToneMap", "tonemap_tables"]
+           "MiToneMap", "ToneMap", "tonemap_tables",
+           "MiResample", "Resample", "RESAMPLE_PRESETS", "RS_TRIANGLE", "RS_CUBIC", "resample_plan", "resample_taps"]

@@ -175,7 +175,7 @@ def fit_crop(w, h, W, H, fit):
 def decode_to_batches(ctx, data, size, batch=8, dtype=None, channels_last=False, mean=None, std=None, fit="stretch",
                       every=1, apply_grain=True, matrix=None, stream=None, inloop_filters=14, threads=1,
                       operating_point=0, all_layers=True, decode_frame_type="all", frame_size_limit=0,
-                      tonemap=None, primaries=None, transfer=None):
+                      tonemap=None, primaries=None, transfer=None, resample=None):
     """Decode a stream on the device and yield (tensor, [MiColorInfo, ...]) batches for an ML
     consumer: the tensor is (n, 3, H, W) with size = (W, H), n = batch except for a shorter last
     one, of `dtype` (torch.float16 by default; bfloat16, float32 or uint8), contiguous or, with
@@ -185,7 +185,9 @@ def decode_to_batches(ctx, data, size, batch=8, dtype=None, channels_last=False,
     stream each get their own crop), resized, normalised with mean / std per channel, with film
     grain when the frame carries it and apply_grain is set. The list holds the colour description
     used for each slot; matrix, tonemap, primaries and transfer follow decode_to_tensors's rules
-    (with tonemap the slot is mi_display_tensor_tm's: the tone-mapped picture, resized). Each tensor is a fresh allocation
+    (with tonemap the slot is mi_display_tensor_tm's: the tone-mapped picture, resized). resample: a
+    MiResample (rav1d_amd.display.Resample, "catmull_rom" for models trained on bicubic-resized
+    inputs): the filter of the resize, None the triangle. Each tensor is a fresh allocation
     the caller owns, filled by work enqueued on `stream` (synchronise it, or stay on it, before
     reading). The other settings are decode_ivf's."""
     import torch
@@ -226,7 +228,8 @@ def decode_to_batches(ctx, data, size, batch=8, dtype=None, channels_last=False,
                         new_batch()
                     display_tensor(ctx, src, state["tensor"][len(state["colors"])], color,
                                    ev.fg if (ev.fg_present and apply_grain) else None,
-                                   fit_crop(src.w, src.h, W, H, fit), mean, std, stream, tonemap=tonemap)
+                                   fit_crop(src.w, src.h, W, H, fit), mean, std, stream, tonemap=tonemap,
+                                   resample=resample)
                     state["colors"].append(color)
                     if len(state["colors"]) == batch:
                         out = state["tensor"], state["colors"]
@@ -246,7 +249,8 @@ def decode_to_batches(ctx, data, size, batch=8, dtype=None, channels_last=False,
 
 
 def decode_to_ladder(ctx, data, sizes, bpc=None, fit="stretch", apply_grain=True, stream=None, inloop_filters=14,
-                     threads=1, operating_point=0, all_layers=True, decode_frame_type="all", frame_size_limit=0):
+                     threads=1, operating_point=0, all_layers=True, decode_frame_type="all", frame_size_limit=0,
+                     resample=None):
     """Decode a stream on the device and yield, per shown picture in output order, (event, rungs):
     the decoder event that showed it and a list with one (Y, UV) pair of device tensors per entry
     of `sizes` ((W, H) luma sizes), the picture as semi-planar YUV at the stream's own subsampling
@@ -255,7 +259,9 @@ def decode_to_ladder(ctx, data, sizes, bpc=None, fit="stretch", apply_grain=True
     stream's); uint8 at 8 bits, else 16-bit words MSB-aligned in int16 storage. fit: fit_crop's,
     per size, moved onto the chroma grid (rav1d_amd.display.even_crop); pictures of different sizes
     in a stream each get their own crops. Film grain is applied once per picture when the frame
-    carries it and apply_grain is set; the chroma siting is the sequence header's. Every tensor is
+    carries it and apply_grain is set; the chroma siting is the sequence header's. resample: a
+    MiResample (rav1d_amd.display.Resample, "mitchell" for instance) for every rung and plane, None
+    the triangle. Every tensor is
     a fresh allocation the caller owns, filled by work enqueued on `stream` (synchronise it, or
     stay on it, before reading). The other settings are decode_ivf's."""
     from .av1dec import MiColorInfo
@@ -279,7 +285,8 @@ def decode_to_ladder(ctx, data, sizes, bpc=None, fit="stretch", apply_grain=True
                 images = [ScaledImage(W, H, src.bpc if bpc is None else bpc, src.layout,
                                       even_crop(fit_crop(src.w, src.h, W, H, fit), src.w, src.h, src.layout))
                           for W, H in sizes]
-                display_scaled(ctx, src, images, color, ev.fg if (ev.fg_present and apply_grain) else None, stream)
+                display_scaled(ctx, src, images, color, ev.fg if (ev.fg_present and apply_grain) else None, stream,
+                               resample=resample)
                 yield ev, [im.tensors() for im in images]
             for i in range(ev.n_release):
                 pics.pop(ev.release[i], None)

@@ -16,7 +16,12 @@ default, more than the 256 MiB Infinity Cache), so every call's source planes co
 Reported per case: microseconds per call, and for the scaled cases the bytes a pass that reads the
 source once and writes the rungs once would move, with the rate they imply at that time.
 
+--filter NAME (triangle, catmull_rom, mitchell, cubic_075: rav1d_amd.display.Resample's presets)
+measures mi_display_scaled_rs and mi_display_tensor_rs with that filter in place of
+mi_display_scaled and mi_display_tensor. Without it the calls are those two.
+
     python tools/scaled_bench.py [--out profiles/scaled_bench.json] [--width 3840 --height 2160]
+                                 [--filter mitchell]
 """
 import argparse
 import ctypes
@@ -42,6 +47,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=24)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--only", default=None, help="run one case without writing --out (for a kernel trace)")
+    ap.add_argument("--filter", default=None, choices=["triangle", "catmull_rom", "mitchell", "cubic_075"],
+                    help="resize through the _rs entries with this filter (default: the entries without one)")
     args = ap.parse_args()
 
     import numpy as np
@@ -49,7 +56,7 @@ def main():
 
     from rav1d_amd import lib
     from rav1d_amd.av1dec import MiColorInfo
-    from rav1d_amd.display import DisplayImage, MiScaledImage, ScaledImage, tensor_image
+    from rav1d_amd.display import DisplayImage, MiScaledImage, Resample, ScaledImage, tensor_image
     from rav1d_amd.frame import Context, Frame
 
     if not torch.cuda.is_available():
@@ -71,6 +78,12 @@ def main():
     sp = ctypes.c_void_p(stream.cuda_stream)
     pics = [s.picture() for s in sources]
     state = dict(k=0)
+    rs = Resample(args.filter) if args.filter else None
+
+    def scaled_entry(pic, ims, n):
+        if rs is not None:
+            return L.mi_display_scaled_rs(ctx.h, pic, ims, n, ctypes.byref(color), ctypes.byref(rs), None, sp)
+        return L.mi_display_scaled(ctx.h, pic, ims, n, ctypes.byref(color), None, sp)
 
     def next_pic():
         state["k"] = (state["k"] + 1) % len(pics)
@@ -90,11 +103,11 @@ def main():
         def fn():
             pic = next_pic()
             if one_call:
-                if L.mi_display_scaled(ctx.h, pic, ims, len(images), ctypes.byref(color), None, sp) != 0:
+                if scaled_entry(pic, ims, len(images)) != 0:
                     raise RuntimeError("mi_display_scaled failed")
             else:
                 for one in singles:
-                    if L.mi_display_scaled(ctx.h, pic, one, 1, ctypes.byref(color), None, sp) != 0:
+                    if scaled_entry(pic, one, 1) != 0:
                         raise RuntimeError("mi_display_scaled failed")
         out_bytes = sum(int(1.5 * W * H) * (1 if obpc == 8 else 2) for W, H in sizes)
         return fn, out_bytes
@@ -105,7 +118,10 @@ def main():
     dim = image.image()
 
     def tensor():
-        if L.mi_display_tensor(ctx.h, next_pic(), ctypes.byref(tim), ctypes.byref(color), None, sp) != 0:
+        if rs is not None:
+            if L.mi_display_tensor_rs(ctx.h, next_pic(), ctypes.byref(tim), ctypes.byref(color), None, ctypes.byref(rs), None, sp) != 0:
+                raise RuntimeError("mi_display_tensor_rs failed")
+        elif L.mi_display_tensor(ctx.h, next_pic(), ctypes.byref(tim), ctypes.byref(color), None, sp) != 0:
             raise RuntimeError("mi_display_tensor failed")
 
     def picture():
@@ -157,7 +173,7 @@ def main():
 
     nv12_us, tensor_us = mean2("scaled_nv12"), mean2("tensor_u8_chw")
     doc = dict(tool="tools/scaled_bench.py", device=torch.cuda.get_device_name(0), width=w, height=h, bpc=bpc,
-               layout="4:2:0", ladder=LADDER, pictures=args.pictures, iters=args.iters, warmup=args.warmup,
+               layout="4:2:0", ladder=LADDER, filter=args.filter, pictures=args.pictures, iters=args.iters, warmup=args.warmup,
                rounds=args.rounds,
                timing="HIP events around back-to-back calls rotating over the source pictures; median of rounds",
                results=results, source_bytes=src_bytes, hbm_peak_gbps=HBM_PEAK_GBS,

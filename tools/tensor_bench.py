@@ -19,7 +19,12 @@ sample. The largest difference is reported over the whole tensor and over its in
 the outermost output row and column on each side, the only ones whose taps leave the picture);
 neither is asserted.
 
+--filter NAME (triangle, catmull_rom, mitchell, cubic_075: rav1d_amd.display.Resample's presets)
+measures mi_display_tensor_rs with that filter in place of mi_display_tensor; the replaced route
+then interpolates with mode="bicubic" for the cubics. Without it the call is mi_display_tensor.
+
     python tools/tensor_bench.py [--out profiles/tensor_bench.json] [--width 3840 --height 2160]
+                                 [--filter catmull_rom]
 """
 import argparse
 import ctypes
@@ -44,6 +49,8 @@ def main():
     ap.add_argument("--iters", type=int, default=120)
     ap.add_argument("--warmup", type=int, default=24)
     ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--filter", default=None, choices=["triangle", "catmull_rom", "mitchell", "cubic_075"],
+                    help="resize through mi_display_tensor_rs with this filter (default: mi_display_tensor)")
     args = ap.parse_args()
 
     import numpy as np
@@ -52,7 +59,7 @@ def main():
 
     from rav1d_amd import lib
     from rav1d_amd.av1dec import MiColorInfo
-    from rav1d_amd.display import DisplayImage, tensor_image
+    from rav1d_amd.display import DisplayImage, Resample, tensor_image
     from rav1d_amd.frame import Context, Frame
 
     if not torch.cuda.is_available():
@@ -84,6 +91,10 @@ def main():
     # the C entries directly, on prebuilt arguments: the host side of a call stays well below the
     # device time, so the events time the device
     targs = [(ctx.h, ctypes.byref(p), ctypes.byref(tim), ctypes.byref(color), None, sp) for p in pics]
+    rs = Resample(args.filter) if args.filter else None
+    rargs = [(ctx.h, ctypes.byref(p), ctypes.byref(tim), ctypes.byref(color), None, ctypes.byref(rs), None, sp)
+             for p in pics] if rs is not None else None
+    mode = "bilinear" if args.filter in (None, "triangle") else "bicubic"
     dargs = [(ctx.h, ctypes.byref(p), ctypes.byref(dim), ctypes.byref(color), None, sp) for p in pics]
     mean_t = torch.tensor(mean, dtype=torch.float32, device="cuda").view(3, 1, 1)
     std_t = torch.tensor(std, dtype=torch.float32, device="cuda").view(3, 1, 1)
@@ -95,7 +106,10 @@ def main():
         return state["k"]
 
     def tensor():
-        if L.mi_display_tensor(*targs[next_k()]) != 0:
+        if rargs is not None:
+            if L.mi_display_tensor_rs(*rargs[next_k()]) != 0:
+                raise RuntimeError("mi_display_tensor_rs failed")
+        elif L.mi_display_tensor(*targs[next_k()]) != 0:
             raise RuntimeError("mi_display_tensor failed")
 
     def rgb_planar():
@@ -106,7 +120,7 @@ def main():
         rgb_planar()
         # (the 16-bit words are held in int16 storage; 10-bit samples are below 2^15)
         x = image.rgb.to(torch.float32).unsqueeze(0)
-        y = F.interpolate(x, size=(oh, ow), mode="bilinear", antialias=True, align_corners=False)[0]
+        y = F.interpolate(x, size=(oh, ow), mode=mode, antialias=True, align_corners=False)[0]
         old.copy_((y / m - mean_t) / std_t)
 
     def timed(fn):
@@ -144,7 +158,7 @@ def main():
     src_bytes = int(1.5 * w * h * pxb)
     t_us = (results["tensor"]["us"] + results["tensor_again"]["us"]) / 2
     doc = dict(tool="tools/tensor_bench.py", device=torch.cuda.get_device_name(0), width=w, height=h, bpc=bpc,
-               layout="4:2:0", out_w=ow, out_h=oh, dtype="float16", order="CHW", pictures=args.pictures,
+               layout="4:2:0", out_w=ow, out_h=oh, dtype="float16", order="CHW", filter=args.filter, pictures=args.pictures,
                iters=args.iters, warmup=args.warmup, rounds=args.rounds,
                timing="HIP events around back-to-back calls rotating over the source pictures; median of rounds",
                results=results, tensor_us=round(t_us, 2), source_bytes=src_bytes,
