@@ -16,6 +16,7 @@ import torch
 
 from . import MiFilmGrainData, MiPicture, check, lib
 from .av1dec import MiColorInfo
+from .frame import _stream_ptr, film_grain_data
 
 OUT_SEMIPLANAR, OUT_RGB_PLANAR, OUT_RGBA_PACKED = 0, 1, 2
 FORMATS = {"nv12": OUT_SEMIPLANAR, "rgb": OUT_RGB_PLANAR, "rgba": OUT_RGBA_PACKED}
@@ -112,6 +113,16 @@ def tonemap_tables(tm, color, src_bpc):
     return lut_in, m.reshape(3, 3), lut_out
 
 
+def _source_args(frame, color, fg):
+    """What every display call passes for its source: (the MiPicture of `frame`, a device Frame or a
+    MiPicture; the pointer to `color` or None; the pointer to the MiFilmGrainData of `fg`, itself
+    or a make_fg_params dict, or None)."""
+    src = frame if isinstance(frame, MiPicture) else frame.picture()
+    if fg is not None and not isinstance(fg, MiFilmGrainData):
+        fg = film_grain_data(fg)
+    return src, ctypes.byref(color) if color is not None else None, ctypes.byref(fg) if fg is not None else None
+
+
 def display_picture(ctx, frame, image, color=None, fg=None, stream=None, tonemap=None):
     """Enqueue mi_display_picture: `frame` (a device Frame or a MiPicture) into `image` (a
     DisplayImage or a MiDisplayImage), with film grain when `fg` (a MiFilmGrainData or a
@@ -120,13 +131,8 @@ def display_picture(ctx, frame, image, color=None, fg=None, stream=None, tonemap
     the call is mi_display_picture_tm, color.pri and color.trc describe the source, and `image`
     holds samples of tonemap.dst_bpc bits (DisplayImage(..., out_bpc=)). Raises MiError on a
     negative return."""
-    from .frame import _stream_ptr, film_grain_data
-    src = frame if isinstance(frame, MiPicture) else frame.picture()
+    src, cp, fp = _source_args(frame, color, fg)
     im = image if isinstance(image, MiDisplayImage) else image.image()
-    if fg is not None and not isinstance(fg, MiFilmGrainData):
-        fg = film_grain_data(fg)
-    cp = ctypes.byref(color) if color is not None else None
-    fp = ctypes.byref(fg) if fg is not None else None
     if tonemap is not None:
         check(lib().mi_display_picture_tm(ctx.h, ctypes.byref(src), ctypes.byref(im), cp, ctypes.byref(tonemap), fp,
                                           _stream_ptr(stream)), "mi_display_picture_tm")
@@ -237,14 +243,9 @@ def display_tensor(ctx, frame, out, color, fg=None, crop=None, mean=None, std=No
     mi_display_tensor_tm, the resized picture is the tone-mapped one and M is 2^dst_bpc - 1.
     resample: a MiResample (Resample()): the call is mi_display_tensor_rs and the resize uses that
     filter; None calls the entries without one (the triangle). Raises MiError on a negative return."""
-    from .frame import _stream_ptr, film_grain_data
-    src = frame if isinstance(frame, MiPicture) else frame.picture()
+    src, cp, fp = _source_args(frame, color, fg)
     bpc = src.bpc if tonemap is None else tonemap.dst_bpc
     im = out if isinstance(out, MiTensorImage) else tensor_image(out, bpc, crop, mean, std, channels_last)
-    if fg is not None and not isinstance(fg, MiFilmGrainData):
-        fg = film_grain_data(fg)
-    cp = ctypes.byref(color) if color is not None else None
-    fp = ctypes.byref(fg) if fg is not None else None
     if resample is not None:
         check(lib().mi_display_tensor_rs(ctx.h, ctypes.byref(src), ctypes.byref(im), cp,
                                          ctypes.byref(tonemap) if tonemap is not None else None, ctypes.byref(resample),
@@ -333,17 +334,12 @@ def display_scaled(ctx, frame, images, color=None, fg=None, stream=None, resampl
     source and of the output). resample: a MiResample (Resample()): the call is
     mi_display_scaled_rs and every plane of every rung is resized with that filter; None calls
     mi_display_scaled (the triangle). Raises MiError on a negative return."""
-    from .frame import _stream_ptr, film_grain_data
-    src = frame if isinstance(frame, MiPicture) else frame.picture()
+    src, cp, fp = _source_args(frame, color, fg)
     if isinstance(images, (ScaledImage, MiScaledImage)):
         images = [images]
     ims = (MiScaledImage * max(len(images), 1))()
     for i, image in enumerate(images):
         ims[i] = image if isinstance(image, MiScaledImage) else image.image()
-    if fg is not None and not isinstance(fg, MiFilmGrainData):
-        fg = film_grain_data(fg)
-    cp = ctypes.byref(color) if color is not None else None
-    fp = ctypes.byref(fg) if fg is not None else None
     if resample is not None:
         check(lib().mi_display_scaled_rs(ctx.h, ctypes.byref(src), ims, len(images), cp, ctypes.byref(resample), fp,
                                          _stream_ptr(stream)), "mi_display_scaled_rs")

@@ -8,9 +8,9 @@ the caller (on the device). There is no CPU pixel path here.
 """
 import ctypes
 
-from . import MiFramePictures, check, lib
+from . import MiFramePictures, MiFrameTiming, check, lib
 from . import frame as F
-from .av1dec import Av1Decoder, stream_units
+from .av1dec import MiColorInfo, stream_events
 
 
 class DevicePictureSet:
@@ -64,26 +64,50 @@ def decode_ivf(ctx, data, stream=None, sync_each=True, inloop_filters=14, thread
     decode_frame_type, frame_size_limit: the Dav1dSettings fields of those names
     (rav1d_amd.av1dec.Av1Decoder). A picture the front-end holds back (all_layers=False) stays in
     `pics` until the event that shows or drops it: the front-end lists it in no release[] before."""
-    dec = Av1Decoder(threads, inloop_filters, operating_point, all_layers, decode_frame_type, frame_size_limit)
+    for _, frame in shown_pictures(ctx, data, stream, sync_each, threads=threads, inloop_filters=inloop_filters,
+                                   operating_point=operating_point, all_layers=all_layers,
+                                   decode_frame_type=decode_frame_type, frame_size_limit=frame_size_limit):
+        yield frame
+
+
+def shown_pictures(ctx, data, stream=None, sync_each=True, **settings):
+    """The decode loop of the generators of this module: every frame of the stream enqueued on
+    the device, and per shown picture, in output order, (ev, frame): the MiDecEvent that shows it
+    (valid until the generator is resumed) and the device Frame. With sync_each every frame is
+    checked with mi_frame_end before anything of it is shown; one mi_frame_end follows the last
+    event. The pictures an event releases are dropped when the consumer resumes the generator: it
+    has taken the shown one by then. settings: stream_events's (threads and the Dav1dSettings
+    fields); the front-end is never more than the current temporal unit ahead."""
     pics = {}
-
-    def consume():
-        for ev in dec.events():
-            if ev.frame:
-                pics[ev.pic_id] = run_frame(ctx, ev.frame.contents, stream, _refs(pics, ev))
-                if sync_each:
-                    frame_end(ctx, stream)
-            if ev.show_pic >= 0:
-                yield pics[ev.show_pic].output()
-            for i in range(ev.n_release):
-                pics.pop(ev.release[i], None)
-
-    for tu in stream_units(data):
-        dec.send(tu)
-        yield from consume()
-    dec.drain()
-    yield from consume()
+    for ev in stream_events(data, lookahead=0, **settings):
+        if ev.frame:
+            pics[ev.pic_id] = run_frame(ctx, ev.frame.contents, stream, _refs(pics, ev))
+            if sync_each:
+                frame_end(ctx, stream)
+        if ev.show_pic >= 0:
+            yield ev, pics[ev.show_pic].output()
+        for i in range(ev.n_release):
+            pics.pop(ev.release[i], None)
     frame_end(ctx, stream)
+
+
+def _grain(ev, apply_grain):
+    """The film grain parameters a shown picture is output with, or None."""
+    return ev.fg if (ev.fg_present and apply_grain) else None
+
+
+def _shown_colour(ev, src, matrix, tonemap, primaries, transfer, rgb):
+    """The MiColorInfo a shown picture is converted with (decode_to_tensors's rules): a copy of the
+    event's; for an RGB output with the matrix override, or the size's default when the stream
+    leaves mtrx unspecified; then with the primaries / transfer overrides."""
+    color = MiColorInfo(*ev.color.astuple())
+    if rgb:
+        if matrix is not None:
+            color.mtrx = int(matrix)
+        elif color.mtrx == 2:
+            color.mtrx = 1 if (src.w >= 1280 or src.h > 576) else 6
+    _source_colour(color, tonemap, primaries, transfer)
+    return color
 
 
 def _source_colour(color, tonemap, primaries, transfer):
@@ -122,40 +146,16 @@ def decode_to_tensors(ctx, data, format="nv12", apply_grain=True, matrix=None, s
     the stream's (as matrix does; the MiColorInfo yielded carries them). With tonemap, a stream
     that leaves either unspecified and has no override raises ValueError. The other settings are
     decode_ivf's."""
-    from .av1dec import MiColorInfo
     from .display import FORMATS, OUT_SEMIPLANAR, DisplayImage, display_picture
     fmt = FORMATS[format] if isinstance(format, str) else int(format)
-    dec = Av1Decoder(threads, inloop_filters, operating_point, all_layers, decode_frame_type, frame_size_limit)
-    pics = {}
-
-    def consume():
-        for ev in dec.events():
-            if ev.frame:
-                pics[ev.pic_id] = run_frame(ctx, ev.frame.contents, stream, _refs(pics, ev))
-                frame_end(ctx, stream)
-            if ev.show_pic >= 0:
-                src = pics[ev.show_pic].output()
-                color = MiColorInfo(*ev.color.astuple())
-                if fmt != OUT_SEMIPLANAR:
-                    if matrix is not None:
-                        color.mtrx = int(matrix)
-                    elif color.mtrx == 2:
-                        color.mtrx = 1 if (src.w >= 1280 or src.h > 576) else 6
-                _source_colour(color, tonemap, primaries, transfer)
-                image = DisplayImage(src.w, src.h, src.bpc, src.layout, fmt,
-                                     out_bpc=tonemap.dst_bpc if tonemap is not None else None)
-                display_picture(ctx, src, image, color, ev.fg if (ev.fg_present and apply_grain) else None, stream,
-                                tonemap)
-                yield image, color
-            for i in range(ev.n_release):
-                pics.pop(ev.release[i], None)
-
-    for tu in stream_units(data):
-        dec.send(tu)
-        yield from consume()
-    dec.drain()
-    yield from consume()
-    frame_end(ctx, stream)
+    for ev, src in shown_pictures(ctx, data, stream, threads=threads, inloop_filters=inloop_filters,
+                                  operating_point=operating_point, all_layers=all_layers,
+                                  decode_frame_type=decode_frame_type, frame_size_limit=frame_size_limit):
+        color = _shown_colour(ev, src, matrix, tonemap, primaries, transfer, rgb=fmt != OUT_SEMIPLANAR)
+        image = DisplayImage(src.w, src.h, src.bpc, src.layout, fmt,
+                             out_bpc=tonemap.dst_bpc if tonemap is not None else None)
+        display_picture(ctx, src, image, color, _grain(ev, apply_grain), stream, tonemap)
+        yield image, color
 
 
 def fit_crop(w, h, W, H, fit):
@@ -192,60 +192,31 @@ def decode_to_batches(ctx, data, size, batch=8, dtype=None, channels_last=False,
     reading). The other settings are decode_ivf's."""
     import torch
 
-    from .av1dec import MiColorInfo
     from .display import display_tensor
     W, H = (int(v) for v in size)
     if batch < 1 or every < 1:
         raise ValueError("batch and every must be at least 1")
     fit_crop(1, 1, W, H, fit)      # (an unknown fit fails before any decoding)
     dtype = torch.float16 if dtype is None else dtype
-    dec = Av1Decoder(threads, inloop_filters, operating_point, all_layers, decode_frame_type, frame_size_limit)
-    pics = {}
-    state = dict(shown=0, tensor=None, colors=[])
-
-    def new_batch():
-        t = torch.empty((batch, 3, H, W), dtype=dtype, device="cuda",
-                        memory_format=torch.channels_last if channels_last else torch.contiguous_format)
-        state["tensor"], state["colors"] = t, []
-
-    def consume():
-        for ev in dec.events():
-            if ev.frame:
-                pics[ev.pic_id] = run_frame(ctx, ev.frame.contents, stream, _refs(pics, ev))
-                frame_end(ctx, stream)
-            if ev.show_pic >= 0:
-                take = state["shown"] % every == 0
-                state["shown"] += 1
-                if take:
-                    src = pics[ev.show_pic].output()
-                    color = MiColorInfo(*ev.color.astuple())
-                    if matrix is not None:
-                        color.mtrx = int(matrix)
-                    elif color.mtrx == 2:
-                        color.mtrx = 1 if (src.w >= 1280 or src.h > 576) else 6
-                    _source_colour(color, tonemap, primaries, transfer)
-                    if state["tensor"] is None:
-                        new_batch()
-                    display_tensor(ctx, src, state["tensor"][len(state["colors"])], color,
-                                   ev.fg if (ev.fg_present and apply_grain) else None,
-                                   fit_crop(src.w, src.h, W, H, fit), mean, std, stream, tonemap=tonemap,
-                                   resample=resample)
-                    state["colors"].append(color)
-                    if len(state["colors"]) == batch:
-                        out = state["tensor"], state["colors"]
-                        state["tensor"] = None
-                        yield out
-            for i in range(ev.n_release):
-                pics.pop(ev.release[i], None)
-
-    for tu in stream_units(data):
-        dec.send(tu)
-        yield from consume()
-    dec.drain()
-    yield from consume()
-    frame_end(ctx, stream)
-    if state["tensor"] is not None:
-        yield state["tensor"][:len(state["colors"])], state["colors"]
+    tensor, colors = None, []
+    shown = enumerate(shown_pictures(ctx, data, stream, threads=threads, inloop_filters=inloop_filters,
+                                     operating_point=operating_point, all_layers=all_layers,
+                                     decode_frame_type=decode_frame_type, frame_size_limit=frame_size_limit))
+    for k, (ev, src) in shown:
+        if k % every:
+            continue
+        color = _shown_colour(ev, src, matrix, tonemap, primaries, transfer, rgb=True)
+        if tensor is None:
+            fmt = torch.channels_last if channels_last else torch.contiguous_format
+            tensor, colors = torch.empty((batch, 3, H, W), dtype=dtype, device="cuda", memory_format=fmt), []
+        display_tensor(ctx, src, tensor[len(colors)], color, _grain(ev, apply_grain),
+                       fit_crop(src.w, src.h, W, H, fit), mean, std, stream, tonemap=tonemap, resample=resample)
+        colors.append(color)
+        if len(colors) == batch:
+            yield tensor, colors
+            tensor = None
+    if tensor is not None:
+        yield tensor[:len(colors)], colors
 
 
 def decode_to_ladder(ctx, data, sizes, bpc=None, fit="stretch", apply_grain=True, stream=None, inloop_filters=14,
@@ -264,39 +235,21 @@ def decode_to_ladder(ctx, data, sizes, bpc=None, fit="stretch", apply_grain=True
     the triangle. Every tensor is
     a fresh allocation the caller owns, filled by work enqueued on `stream` (synchronise it, or
     stay on it, before reading). The other settings are decode_ivf's."""
-    from .av1dec import MiColorInfo
     from .display import ScaledImage, display_scaled, even_crop
     sizes = [(int(W), int(H)) for W, H in sizes]
     if not 1 <= len(sizes) <= 8:
         raise ValueError("1 to 8 sizes")
     for W, H in sizes:
         fit_crop(1, 1, W, H, fit)      # (an unknown fit fails before any decoding)
-    dec = Av1Decoder(threads, inloop_filters, operating_point, all_layers, decode_frame_type, frame_size_limit)
-    pics = {}
-
-    def consume():
-        for ev in dec.events():
-            if ev.frame:
-                pics[ev.pic_id] = run_frame(ctx, ev.frame.contents, stream, _refs(pics, ev))
-                frame_end(ctx, stream)
-            if ev.show_pic >= 0:
-                src = pics[ev.show_pic].output()
-                color = MiColorInfo(*ev.color.astuple())
-                images = [ScaledImage(W, H, src.bpc if bpc is None else bpc, src.layout,
-                                      even_crop(fit_crop(src.w, src.h, W, H, fit), src.w, src.h, src.layout))
-                          for W, H in sizes]
-                display_scaled(ctx, src, images, color, ev.fg if (ev.fg_present and apply_grain) else None, stream,
-                               resample=resample)
-                yield ev, [im.tensors() for im in images]
-            for i in range(ev.n_release):
-                pics.pop(ev.release[i], None)
-
-    for tu in stream_units(data):
-        dec.send(tu)
-        yield from consume()
-    dec.drain()
-    yield from consume()
-    frame_end(ctx, stream)
+    for ev, src in shown_pictures(ctx, data, stream, threads=threads, inloop_filters=inloop_filters,
+                                  operating_point=operating_point, all_layers=all_layers,
+                                  decode_frame_type=decode_frame_type, frame_size_limit=frame_size_limit):
+        images = [ScaledImage(W, H, src.bpc if bpc is None else bpc, src.layout,
+                              even_crop(fit_crop(src.w, src.h, W, H, fit), src.w, src.h, src.layout))
+                  for W, H in sizes]
+        display_scaled(ctx, src, images, MiColorInfo(*ev.color.astuple()), _grain(ev, apply_grain), stream,
+                       resample=resample)
+        yield ev, [im.tensors() for im in images]
 
 
 _extra_lanes = {}
@@ -313,6 +266,24 @@ def _lanes(ctx, stream, n):
         from .frame import Context
         extra.append((Context(torch.cuda.current_device()), torch.cuda.Stream()))
     return lanes + extra[:n - 1]
+
+
+def _lane_timing(lanes):
+    """The mi_ctx_timing figures of every lane's context summed under decode_to_muxer's stats
+    keys; switches the contexts' timing off again."""
+    tot = dict(frames=0, run_host_ms=0.0, upload_ms=0.0, inter_ms=0.0, intra_ms=0.0, filter_ms=0.0,
+               upload_bytes=0, run_stage_ms=0.0, run_levels_ms=0.0)
+    for lctx, _ in lanes:
+        tm = MiFrameTiming()
+        check(lib().mi_ctx_timing(lctx.h, ctypes.byref(tm)), "mi_ctx_timing")
+        check(lib().mi_ctx_set_timing(lctx.h, 0), "mi_ctx_set_timing")
+        tot["frames"] += tm.frames
+        tot["run_host_ms"] += tm.host_ms
+        tot["run_stage_ms"] += tm.stage_ms
+        tot["run_levels_ms"] += tm.strips_ms
+        for f in ("upload_ms", "inter_ms", "intra_ms", "filter_ms", "upload_bytes"):
+            tot[f] += getattr(tm, f)
+    return tot
 
 
 def decode_to_muxer(ctx, data, muxer, stream=None, apply_grain=True, pipelined=True, threads=8, in_flight=2,
@@ -347,8 +318,6 @@ def decode_to_muxer(ctx, data, muxer, stream=None, apply_grain=True, pipelined=T
     time (mux_ms)."""
     import time
 
-    from . import MiFrameTiming
-    from .av1dec import stream_events
     from .output import HostPicture, output_picture
     import torch
     if not pipelined:
@@ -416,7 +385,7 @@ def decode_to_muxer(ctx, data, muxer, stream=None, apply_grain=True, pipelined=T
             h = hosts[slot]
             if h is None or (h.pic.w, h.pic.h, h.pic.bpc, h.pic.layout) != (out.w, out.h, out.bpc, out.layout):
                 hosts[slot] = h = HostPicture(out.w, out.h, out.bpc, out.layout)
-            fg = ev.fg if (ev.fg_present and apply_grain) else None
+            fg = _grain(ev, apply_grain)
             if stats is not None:
                 a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 a.record(streams[li])
@@ -436,18 +405,7 @@ def decode_to_muxer(ctx, data, muxer, stream=None, apply_grain=True, pipelined=T
     for lctx, lst in lanes:
         frame_end(lctx, lst)
     if stats is not None:
-        tot = dict(frames=0, run_host_ms=0.0, upload_ms=0.0, inter_ms=0.0, intra_ms=0.0, filter_ms=0.0,
-                   upload_bytes=0, run_stage_ms=0.0, run_levels_ms=0.0)
-        for lctx, _ in lanes:
-            tm = MiFrameTiming()
-            check(lib().mi_ctx_timing(lctx.h, ctypes.byref(tm)), "mi_ctx_timing")
-            check(lib().mi_ctx_set_timing(lctx.h, 0), "mi_ctx_set_timing")
-            tot["frames"] += tm.frames
-            tot["run_host_ms"] += tm.host_ms
-            tot["run_stage_ms"] += tm.stage_ms
-            tot["run_levels_ms"] += tm.strips_ms
-            for f in ("upload_ms", "inter_ms", "intra_ms", "filter_ms", "upload_bytes"):
-                tot[f] += getattr(tm, f)
+        tot = _lane_timing(lanes)
         acc["d2h_ms"] = sum(a.elapsed_time(b) for a, b in out_ev)
         stats.update(tot)
         stats.update(acc)

@@ -2,15 +2,22 @@
 driver (oracle/decode.c), hashed like the reference's md5 muxer (tools/output/md5.rs:541-637).
 
 TEST INFRASTRUCTURE ONLY: this is the checker that pins the CPU restatement (and, through it,
-the GPU path) to the reference's own MD5 vectors (tests/dav1d-test-data/**/meson.build).
+the GPU path) to the reference's own MD5 vectors (tests/dav1d-test-data/**/meson.build). Also what
+the GPU stream suites share: stream(), and the planar pictures decode_to_muxer writes for a vector
+(Capture, planar_pictures), computed once per vector.
 """
 import ctypes
 import hashlib
+import json
+import os
 
 import numpy as np
 
 from rav1d_amd.av1dec import MiDecFrame
 from tests import oracle_lib
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "streams")
+VECTORS = {v["name"]: v for v in json.load(open(os.path.join(GOLDEN, "vectors.json")))}
 
 
 def _bind(o):
@@ -121,3 +128,42 @@ def decode_stream(data, recon=oracle_frame, max_frames=None, threads=1, apply_gr
     if shown:
         assert digest == md5.hexdigest(), "md5 muxer disagrees with hashlib"
     return digest if shown else md5.hexdigest(), shown
+
+
+def stream(name):
+    """(vector, bytes) of a stream of tests/golden/streams."""
+    v = VECTORS[name]
+    return v, open(os.path.join(GOLDEN, v["file"]), "rb").read()
+
+
+class Capture:
+    """A muxer that keeps the planar pictures decode_to_muxer writes (visible area, host copies)."""
+
+    def __init__(self):
+        self.pictures = []
+
+    def write(self, pic):
+        pxb = 1 if pic.bpc == 8 else 2
+        ss_hor, ss_ver = int(pic.layout in (1, 2)), int(pic.layout == 1)
+        planes = []
+        for p in range(3 if pic.layout else 1):
+            w, h = (pic.w, pic.h) if p == 0 else ((pic.w + ss_hor) >> ss_hor, (pic.h + ss_ver) >> ss_ver)
+            st = pic.stride[1 if p else 0]
+            raw = np.ctypeslib.as_array((ctypes.c_uint8 * (st * h)).from_address(pic.data[p])).reshape(h, st)
+            rows = raw[:, :w * pxb].copy()
+            planes.append(rows.view("<u2") if pxb == 2 else rows)
+        self.pictures.append((planes, pic.bpc, pic.layout))
+
+
+_planar = {}
+
+
+def planar_pictures(gpu, name):
+    """The reference pictures of a vector, computed once and shared."""
+    from rav1d_amd.stream import decode_to_muxer
+    if name not in _planar:
+        v, data = stream(name)
+        cap = Capture()
+        assert decode_to_muxer(gpu, data, cap, apply_grain=bool(v.get("filmgrain"))) == len(cap.pictures) > 0
+        _planar[name] = cap.pictures
+    return _planar[name]

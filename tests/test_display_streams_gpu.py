@@ -2,61 +2,19 @@
 de-interleaved on the host and fed to the product md5 muxer, give the reference's MD5 of the
 vector; the RGB tensors equal tests/display_ref.py applied to the planar pictures
 decode_to_muxer writes for the same stream."""
-import ctypes
-import json
-import os
-
 import numpy as np
 import pytest
 import torch
 
 from rav1d_amd.output import Muxer, host_picture_np
-from rav1d_amd.stream import decode_to_muxer, decode_to_tensors
+from rav1d_amd.stream import decode_to_tensors
 from tests import display_ref as R
+from tests.stream_lib import planar_pictures, stream
 
 pytestmark = pytest.mark.gpu
 
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "streams")
-VECTORS = {v["name"]: v for v in json.load(open(os.path.join(GOLDEN, "vectors.json")))}
 # 8-bit 4:2:0, 10-bit 4:2:0, 10-bit 4:4:4, 8-bit monochrome, film grain (8-bit 4:2:0, odd width)
 NAMES = ["av1-1-b8-01-size-18x16", "av1-1-b10-00-quantizer-63", "00000943_10bit", "00001105", "309_odd_width"]
-
-
-def stream(name):
-    v = VECTORS[name]
-    return v, open(os.path.join(GOLDEN, v["file"]), "rb").read()
-
-
-class Capture:
-    """A muxer that keeps the planar pictures decode_to_muxer writes (visible area, host copies)."""
-
-    def __init__(self):
-        self.pictures = []
-
-    def write(self, pic):
-        pxb = 1 if pic.bpc == 8 else 2
-        ss_hor, ss_ver = int(pic.layout in (1, 2)), int(pic.layout == 1)
-        planes = []
-        for p in range(3 if pic.layout else 1):
-            w, h = (pic.w, pic.h) if p == 0 else ((pic.w + ss_hor) >> ss_hor, (pic.h + ss_ver) >> ss_ver)
-            st = pic.stride[1 if p else 0]
-            raw = np.ctypeslib.as_array((ctypes.c_uint8 * (st * h)).from_address(pic.data[p])).reshape(h, st)
-            rows = raw[:, :w * pxb].copy()
-            planes.append(rows.view("<u2") if pxb == 2 else rows)
-        self.pictures.append((planes, pic.bpc, pic.layout))
-
-
-_planar = {}
-
-
-def planar_pictures(gpu, name):
-    """The reference pictures of a vector, computed once and shared."""
-    if name not in _planar:
-        v, data = stream(name)
-        cap = Capture()
-        assert decode_to_muxer(gpu, data, cap, apply_grain=bool(v.get("filmgrain"))) == len(cap.pictures) > 0
-        _planar[name] = cap.pictures
-    return _planar[name]
 
 
 @pytest.mark.parametrize("name", NAMES)

@@ -8,8 +8,9 @@ from rav1d_amd.display import Resample, even_crop
 from rav1d_amd.stream import decode_to_batches, decode_to_ladder, fit_crop
 from tests import cubic_ref as C
 from tests import tensor_ref as T
+from tests.stream_lib import planar_pictures, stream
 from tests.test_scaled_streams_gpu import host, one_to_one_pictures
-from tests.test_tensor_streams_gpu import MEAN, STD, planar_pictures, stream
+from tests.test_tensor_streams_gpu import MEAN, STD
 
 pytestmark = pytest.mark.gpu
 

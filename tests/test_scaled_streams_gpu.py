@@ -1,9 +1,6 @@
 """GPU: whole streams through decode_to_ladder (rav1d_amd/stream.py): every shown picture's rungs
 equal tests/scaled_ref.py applied to the pictures the same stream gives through the existing 1:1
 path (decode_to_tensors, semi-planar), in the same number and order."""
-import json
-import os
-
 import numpy as np
 import pytest
 import torch
@@ -11,17 +8,9 @@ import torch
 from rav1d_amd.display import even_crop
 from rav1d_amd.stream import decode_to_ladder, decode_to_tensors, fit_crop
 from tests import scaled_ref as Z
+from tests.stream_lib import stream
 
 pytestmark = pytest.mark.gpu
-
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "streams")
-VECTORS = {v["name"]: v for v in json.load(open(os.path.join(GOLDEN, "vectors.json")))}
-
-
-def stream(name):
-    v = VECTORS[name]
-    return v, open(os.path.join(GOLDEN, v["file"]), "rb").read()
-
 
 _pictures = {}
 

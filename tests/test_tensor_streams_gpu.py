@@ -1,61 +1,19 @@
 """GPU: whole streams through decode_to_batches (rav1d_amd/stream.py): every `every`-th shown
 picture as a slot of a float16 batch, equal bit for bit to tests/tensor_ref.py applied to the
 planar pictures decode_to_muxer writes for the same stream, for both `fit` values."""
-import ctypes
-import json
-import os
-
 import numpy as np
 import pytest
 import torch
 
-from rav1d_amd.stream import decode_to_batches, decode_to_muxer, fit_crop
+from rav1d_amd.stream import decode_to_batches, fit_crop
 from tests import tensor_ref as T
+from tests.stream_lib import planar_pictures, stream
 
 pytestmark = pytest.mark.gpu
 
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "streams")
-VECTORS = {v["name"]: v for v in json.load(open(os.path.join(GOLDEN, "vectors.json")))}
 # 8-bit 4:2:0, 10-bit 4:2:0, film grain (8-bit 4:2:0, odd width)
 NAMES = ["av1-1-b8-01-size-18x16", "av1-1-b10-00-quantizer-63", "309_odd_width"]
 MEAN, STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
-
-
-def stream(name):
-    v = VECTORS[name]
-    return v, open(os.path.join(GOLDEN, v["file"]), "rb").read()
-
-
-class Capture:
-    """A muxer that keeps the planar pictures decode_to_muxer writes (visible area, host copies)."""
-
-    def __init__(self):
-        self.pictures = []
-
-    def write(self, pic):
-        pxb = 1 if pic.bpc == 8 else 2
-        ss_hor, ss_ver = int(pic.layout in (1, 2)), int(pic.layout == 1)
-        planes = []
-        for p in range(3 if pic.layout else 1):
-            w, h = (pic.w, pic.h) if p == 0 else ((pic.w + ss_hor) >> ss_hor, (pic.h + ss_ver) >> ss_ver)
-            st = pic.stride[1 if p else 0]
-            raw = np.ctypeslib.as_array((ctypes.c_uint8 * (st * h)).from_address(pic.data[p])).reshape(h, st)
-            rows = raw[:, :w * pxb].copy()
-            planes.append(rows.view("<u2") if pxb == 2 else rows)
-        self.pictures.append((planes, pic.bpc, pic.layout))
-
-
-_planar = {}
-
-
-def planar_pictures(gpu, name):
-    """The reference pictures of a vector, computed once and shared."""
-    if name not in _planar:
-        v, data = stream(name)
-        cap = Capture()
-        assert decode_to_muxer(gpu, data, cap, apply_grain=bool(v.get("filmgrain"))) == len(cap.pictures) > 0
-        _planar[name] = cap.pictures
-    return _planar[name]
 
 
 def check_batches(gpu, name, fit, size):

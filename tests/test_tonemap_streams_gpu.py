@@ -12,7 +12,7 @@ from rav1d_amd.stream import decode_to_batches, decode_to_tensors
 from tests import display_ref as R
 from tests import tensor_ref as T
 from tests import tonemap_ref as TM
-from tests.test_tensor_streams_gpu import planar_pictures, stream
+from tests.stream_lib import planar_pictures, stream
 
 pytestmark = pytest.mark.gpu
 
