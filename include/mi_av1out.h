@@ -4,8 +4,8 @@
  *
  * Two libraries implement it:
  *   - librav1d_amd.so (gfx950): mi_host_picture_alloc / _free, mi_output_picture, and the
- *     output that stays on the device, mi_display_picture, mi_display_tensor and
- *     mi_display_scaled;
+ *     output that stays on the device, mi_display_picture, mi_display_tensor,
+ *     mi_display_scaled and the tone-mapped mi_display_yuv_tm / mi_display_scaled_tm;
  *   - libmi_av1dec.so (host C++): the muxers mi_muxer_* (no GPU code).
  *
  * Reference: the CLI's output stage (tools/output/output.rs), its muxers md5
@@ -357,6 +357,72 @@ int mi_resample_plan(const MiResample *rs, int n_in, int n_out, int *cap, int *s
  * for a NULL table, a phase other than 2 and 4, and a `cap` below mi_resample_plan's. */
 int mi_resample_taps(const MiResample *rs, int n_in, int n_out, int phase, int cap,
                      int32_t *start, int32_t *count, int32_t *k /* [cap][n_out] */);
+
+/* ---- tone-mapped YUV output (librav1d_amd.so) ---------------------------------------------- */
+
+/* The colour-volume stage with a Y'CbCr result, for an encoder on the device: an HDR10 source to
+ * SDR semi-planar YUV, 1:1 (mi_display_yuv_tm) or as the rungs of a ladder (mi_display_scaled_tm).
+ * Both are defined through the picture Q:
+ *
+ * P is the w x h R'G'B' picture mi_display_picture_tm gives as MI_OUT_RGB_PLANAR for the same
+ * `in`, `color`, `tm` and `fg` (the upsampler, the matrix of color->mtrx, identity and 4:0:0
+ * included, the stage; film grain applied once, to the source, before all of it).
+ * d = tm->dst_bpc, Md = 2^d - 1, H = 2^(d-1), S = 14. The target is MiYuvTarget: mtrx one of 1, 4,
+ * 5, 6, 7, 9 with the Kr, Kb of the inverse direction above; range 0 (limited) or 1 (full). Q has
+ * the source's layout (sh, sv the subsampling shifts), depth d, and chroma size cw x ch =
+ * ((w + sh) >> sh, (h + sv) >> sv). A source with color->mtrx == 0 (GBR, 4:4:4) is a valid source:
+ * Q carries the target's matrix.
+ *
+ * Forward matrix, at full resolution on the integers of P. Kg = 1 - Kr - Kb; limited: Yo =
+ * 16 << (d-8), sy = (219 << (d-8)) / Md, sc = (224 << (d-8)) / Md; full: Yo = 0, sy = sc = 1. The
+ * coefficients are computed on the host in double precision and rounded once (round(x) =
+ * floor(x + 0.5)):
+ *   yr = round(2^S Kr sy), yb = round(2^S Kb sy), yg = round(2^S sy) - yr - yb;
+ *   ur = -round(2^S sc Kr / (2 (1-Kb))), ug = -round(2^S sc Kg / (2 (1-Kb))), ub = -(ur + ug);
+ *   vg = -round(2^S sc Kg / (2 (1-Kr))), vb = -round(2^S sc Kb / (2 (1-Kr))), vr = -(vg + vb);
+ * so grey maps to chroma H exactly and white to the top of the luma range.
+ *   Y  = clip(((yr R + yg G + yb B + 2^(S-1)) >> S) + Yo, 0, Md)
+ *   U4 = clip(((ur R + ug G + ub B + 2^(S-1)) >> S) + H, 0, Md)
+ *   V4 = clip(((vr R + vg G + vb B + 2^(S-1)) >> S) + H, 0, Md)
+ * (an arithmetic shift of a signed 32-bit sum, which fits: three coefficients of at most 2^14
+ * times 4095).
+ *
+ * Chroma decimation of U4 and V4 (w x h each) to cw x ch: one 2-D integer filter per output sample
+ * (i, j), rounded once, indices clamped, so no pass order is implied.
+ *   horizontal, 4:2:0 and 4:2:2 (co-sited, the siting the upsampler and mi_display_scaled assume):
+ *     weights (1, 2, 1) on columns max(2i-1, 0), 2i, min(2i+1, w-1);
+ *   vertical, 4:2:0, chr == 2 (co-located): (1, 2, 1) on rows max(2j-1, 0), 2j, min(2j+1, h-1);
+ *   vertical, 4:2:0, chr 0 or 1 (centred): (1, 1) on rows 2j, min(2j+1, h-1);
+ *   an axis that is not subsampled: weight 1 on its own sample.
+ *   C[j][i] = (sum wx wy C4[row][column] + W/2) >> log2(W), W = sum wx wy (2, 4, 8 or 16).
+ * 4:4:4: U = U4, V = V4. 4:0:0: Q has Y only (R = G = B comes out of the matrix, and the stage
+ * still runs on it). */
+typedef struct MiYuvTarget { int32_t mtrx, range; } MiYuvTarget;
+
+/* Enqueue Q on `stream` (never synchronises) in the storage of MI_OUT_SEMIPLANAR: out->format must
+ * be MI_OUT_SEMIPLANAR and out->bpc == tm->dst_bpc; data[0] = Y, data[1] = interleaved UV at the
+ * source's subsampling (not read for 4:0:0), u8 at 8 bits, else u16 MSB-aligned. Only the w x h
+ * luma samples and the cw x ch UV pairs are written, straight from the kernel that computes them.
+ * The checks of mi_display_picture_tm apply (its colour-matrix rules for the source, the rules of
+ * the stage: -ENOTSUP for the pri and trc values listed there), all before any device work, the NULL
+ * `ctx` last; in addition -EINVAL for NULL `tm` or `target`, a target->mtrx outside the list (0, 2,
+ * 8, 10 - 14 and reserved values alike: the caller chooses the output, nothing is unsupported on
+ * the source's behalf), a target->range outside 0 / 1, an out->format other than
+ * MI_OUT_SEMIPLANAR, out->bpc != tm->dst_bpc, NULL data[1] with a chroma layout. */
+int mi_display_yuv_tm(MiCtx *ctx, const MiPicture *in, const MiDisplayImage *out,
+                      const MiColorInfo *color, const MiToneMap *tm, const MiYuvTarget *target,
+                      const MiFilmGrainData *fg, void *stream);
+
+/* mi_display_scaled_rs(ctx, Q, outs, n_outs, color, rs, NULL, stream), bit for bit: Q a planar
+ * picture of depth d in a scratch the context owns (allocated on first use, replaced only when a
+ * call needs more, shared with no other scratch), written by one kernel in front of the scaled
+ * passes on the same stream. Ms of the scaled definition is Md and a rung's bpc converts from d;
+ * `color` as passed (the scaled passes read its chr, the siting of Q and of the rungs). The checks
+ * are those of mi_display_scaled_rs and of mi_display_yuv_tm's source, tone map and target, all
+ * before any device work, the NULL `ctx` last. */
+int mi_display_scaled_tm(MiCtx *ctx, const MiPicture *in, const MiScaledImage *outs, int n_outs,
+                         const MiColorInfo *color, const MiToneMap *tm, const MiYuvTarget *target,
+                         const MiResample *rs, const MiFilmGrainData *fg, void *stream);
 
 #ifdef __cplusplus
 }

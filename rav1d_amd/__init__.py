@@ -241,6 +241,11 @@ def lib():
     _sig(L, "mi_resample_plan", ctypes.c_int, [_VP, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
                                                ctypes.POINTER(ctypes.c_int)])
     _sig(L, "mi_resample_taps", ctypes.c_int, [_VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP])
+    # (MiYuvTarget: rav1d_amd/display.py)
+    _sig(L, "mi_display_yuv_tm", ctypes.c_int, [_VP, ctypes.POINTER(MiPicture), _VP, _VP, _VP, _VP,
+                                                ctypes.POINTER(MiFilmGrainData), _VP])
+    _sig(L, "mi_display_scaled_tm", ctypes.c_int, [_VP, ctypes.POINTER(MiPicture), _VP, ctypes.c_int, _VP, _VP, _VP, _VP,
+                                                   ctypes.POINTER(MiFilmGrainData), _VP])
     _lib = L
     return L
 
@@ -259,7 +264,8 @@ EXPORTED = ["mi_version", "mi_ctx_create", "mi_ctx_destroy", "mi_ctx_last_error"
             "mi_dsp_fg_generate_grain_y", "mi_dsp_fg_generate_grain_uv", "mi_dsp_fgy_32x32xn", "mi_dsp_fguv_32x32xn",
             "mi_host_picture_alloc", "mi_host_picture_free", "mi_output_picture", "mi_display_picture",
             "mi_display_tensor", "mi_tonemap_tables", "mi_display_picture_tm", "mi_display_tensor_tm",
-            "mi_display_scaled", "mi_display_tensor_rs", "mi_display_scaled_rs", "mi_resample_plan", "mi_resample_taps"]
+            "mi_display_scaled", "mi_display_tensor_rs", "mi_display_scaled_rs", "mi_resample_plan", "mi_resample_taps",
+            "mi_display_yuv_tm", "mi_display_scaled_tm"]
 
 
 def check(rc, what):

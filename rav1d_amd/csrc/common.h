@@ -525,6 +525,19 @@ template <bool TM> using ToneParam = typename ToneSel<TM>::type;
 // RGB formats only; the destination samples are u8 at dst_bpc 8, else u16
 int launch_display_tm(const DisplayArgs &a, const ToneArgs &tm, int bpc, int dst_bpc, int format, hipStream_t s);
 
+// tone-mapped YUV output (yuv_tm.hip): after the colour-volume stage the forward matrix to the
+// target's Y'CbCr (14-bit fixed point, include/mi_av1out.h "the picture Q") and the chroma
+// decimation back to the source's subsampling. DisplayArgs carries the source half, the inverse
+// matrix and the destination planes (dst[0] = Y; dst[1] = interleaved UV, or dst[1] / dst[2] = the
+// U and V planes of the context's scratch picture).
+struct YuvArgs {
+    int yr, yg, yb, ur, ug, ub, vr, vg, vb;
+    int yo, half, maxd;           // Yo, H and Md of the destination depth
+    int shift;                    // interleaved store: 16 - d for d > 8, else 0
+};
+// planar: the scratch picture (samples LSB-aligned, u8 at dst_bpc 8, else u16); else semi-planar
+int launch_yuv_tm(const DisplayArgs &a, const ToneArgs &tm, const YuvArgs &f, int bpc, int dst_bpc, bool planar, hipStream_t s);
+
 // the separable resize of the tensor and scaled outputs (resize.h): one axis of a tap table, and
 // the list of axes one launch of the taps kernel fills (a scaled call: up to 8 rungs of luma x,
 // luma y, chroma x, chroma y)

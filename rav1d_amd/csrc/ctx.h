@@ -67,6 +67,10 @@ struct MiCtx {
     // the geometry of the shown picture, replaced only when a picture needs more)
     uint8_t *disp_fg = nullptr;
     size_t disp_fg_bytes = 0;
+    // mi_display_scaled_tm: the tone-mapped picture Q the scaled passes read (planar, at dst_bpc;
+    // one allocation of its own, replaced only when a call needs more)
+    uint8_t *disp_q = nullptr;
+    size_t disp_q_bytes = 0;
     // mi_display_tensor and mi_display_scaled: a scratch each, so that alternating calls of the
     // two keep their tables
     MiResizeScratch tens, scal;
@@ -138,6 +142,7 @@ struct MiCtx {
         if (fg_scaling) (void)hipFree(fg_scaling);
         if (fg_offsets) (void)hipFree(fg_offsets);
         if (disp_fg) (void)hipFree(disp_fg);
+        if (disp_q) (void)hipFree(disp_q);
         if (tens.p) (void)hipFree(tens.p);
         if (scal.p) (void)hipFree(scal.p);
         if (tone_dev) (void)hipFree(tone_dev);

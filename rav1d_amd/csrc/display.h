@@ -1,7 +1,8 @@
 // display.h — what the device outputs share. All of them (display.hip mi_display_picture,
 // tensor.hip mi_display_tensor, scaled.hip mi_display_scaled): the checks of the source picture
-// and of a crop, the film-grain step, vector loads of a plane run. The R'G'B' outputs
-// (mi_display_picture, mi_display_tensor): the host side of the conversion (colour checks and
+// and of a crop, the film-grain step, vector loads and stores of a plane run. The R'G'B' outputs
+// (mi_display_picture, mi_display_tensor) and the tone-mapped YUV outputs that continue from their
+// picture (yuv_tm.hip mi_display_yuv_tm, mi_display_scaled_tm): the host side of the conversion (colour checks and
 // 14-bit coefficients, the source half of DisplayArgs) and its device side (the integer chroma
 // upsampler, the matrix, the colour-volume stage), so both compute the same picture. The resize of
 // the tensor and scaled outputs is resize.h.
@@ -33,6 +34,11 @@ inline bool aligned_to(const void *p, ptrdiff_t stride, uintptr_t n) { return ((
 // is not 0 / 1, identity without 4:4:4; -ENOTSUP for matrices 8 and 10-14; else 0 with a.identity
 // or a.yo / a.ky / a.crv / a.cbu / a.cgu / a.cgv set. No device work.
 int display_color(const MiPicture *in, const MiColorInfo *color, DisplayArgs &a);
+// (Kr, Kb) of a Dav1dMatrixCoefficients value, the one table of both directions of the matrix: 0,
+// -ENOTSUP (defined, but no Kr / Kb matrix: 8, 10-14) or -EINVAL (0, 2, reserved)
+int matrix_k(int mtrx, double *kr, double *kb);
+// v in 14-bit fixed point, rounded to nearest
+int round_fix(double v);
 // The source half of DisplayArgs: planes, strides, vector-load flags, sizes, siting, H and M.
 void display_source(const MiPicture &src, const MiColorInfo *color, DisplayArgs &a);
 
@@ -43,6 +49,22 @@ int tone_check(const MiToneMap *tm, const MiColorInfo *color);
 // The context's device tables for (tm, color, src_bpc), all checked before: built and uploaded on
 // `s` when they differ from the ones it holds. 0, -ENOMEM or -EIO (with last_error set).
 int tone_prepare(MiCtx *ctx, const MiToneMap *tm, const MiColorInfo *color, int src_bpc, hipStream_t s, ToneArgs &t);
+
+// ---- host (yuv_tm.hip) ----
+// The rules of the tone-mapped YUV outputs beyond their plain entries': -EINVAL for NULL `tm` or
+// `target`, the colour rules of the RGB formats (display_color) and of the stage (tone_check), then
+// -EINVAL for a target matrix that is no Kr / Kb matrix or a range that is not 0 / 1; else 0 with
+// the inverse matrix in `a` and the forward coefficients in `f`. No device work.
+int yuv_tm_check(const MiPicture *in, const MiColorInfo *color, const MiToneMap *tm, const MiYuvTarget *target,
+                 DisplayArgs &a, YuvArgs &f);
+// The context's scratch picture for Q of `in` at dst_bpc in *q (planar, 128-byte aligned rows),
+// allocated or grown: 0 or -ENOMEM (with last_error set). Nothing launched.
+int yuv_tm_scratch(MiCtx *ctx, const MiPicture *in, int dst_bpc, MiPicture *q);
+// Enqueue Q of `src` (the source, grained where the call has grain) on `s`: into the planes of `q`
+// (planar) or into dst[0] = Y and dst[1] = interleaved UV with the strides given (q NULL). `a` and
+// `f` from yuv_tm_check, `tm` from tone_prepare. 0 or -1.
+int yuv_tm_picture(const MiPicture &src, const MiColorInfo *color, DisplayArgs a, const ToneArgs &tm, const YuvArgs &f,
+                   const MiPicture *q, void *const dst[2], const ptrdiff_t dstride[2], int dst_bpc, hipStream_t s);
 
 // ---- device ----
 
@@ -106,6 +128,38 @@ __device__ __forceinline__ void load_run(const uint8_t *row, int x0, int pw, boo
     } else {
 #pragma unroll
         for (int k = 0; k < N; k++) v[k] = (int)p[min(x0 + k, pw - 1)];
+    }
+}
+
+// N samples to a destination row at sample s0; the row holds `limit` samples
+template <typename Px, int N>
+__device__ __forceinline__ void store_run(uint8_t *row, int s0, int limit, bool vec, const int (&v)[N]) {
+    Px *p = reinterpret_cast<Px *>(row);
+    constexpr int kBytes = N * (int)sizeof(Px);
+    static_assert(kBytes == 4 || kBytes == 8 || kBytes % 16 == 0, "whole vectors per run");
+    if (vec && s0 + N <= limit) {
+        uint32_t q[kBytes / 4];
+#pragma unroll
+        for (int i = 0; i < kBytes / 4; i++) {
+            if constexpr (sizeof(Px) == 1)
+                q[i] = (uint32_t)v[4 * i] | ((uint32_t)v[4 * i + 1] << 8) | ((uint32_t)v[4 * i + 2] << 16) |
+                       ((uint32_t)v[4 * i + 3] << 24);
+            else
+                q[i] = (uint32_t)v[2 * i] | ((uint32_t)v[2 * i + 1] << 16);
+        }
+        if constexpr (kBytes == 4) {
+            *reinterpret_cast<uint32_t *>(p + s0) = q[0];
+        } else if constexpr (kBytes == 8) {
+            *reinterpret_cast<uint2 *>(p + s0) = make_uint2(q[0], q[1]);
+        } else {
+#pragma unroll
+            for (int i = 0; i < kBytes / 16; i++)
+                reinterpret_cast<uint4 *>(p + s0)[i] = make_uint4(q[4 * i], q[4 * i + 1], q[4 * i + 2], q[4 * i + 3]);
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < N; k++)
+            if (s0 + k < limit) p[s0 + k] = (Px)v[k];
     }
 }
 

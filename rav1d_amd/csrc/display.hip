@@ -26,36 +26,6 @@
 namespace mi {
 namespace {
 
-// N samples to a destination row at sample s0; the row holds `limit` samples
-template <typename Px, int N>
-__device__ __forceinline__ void store_run(uint8_t *row, int s0, int limit, bool vec, const int (&v)[N]) {
-    Px *p = reinterpret_cast<Px *>(row);
-    constexpr int kBytes = N * (int)sizeof(Px);
-    static_assert(kBytes == 8 || kBytes % 16 == 0, "whole vectors per run");
-    if (vec && s0 + N <= limit) {
-        uint32_t q[kBytes / 4];
-#pragma unroll
-        for (int i = 0; i < kBytes / 4; i++) {
-            if constexpr (sizeof(Px) == 1)
-                q[i] = (uint32_t)v[4 * i] | ((uint32_t)v[4 * i + 1] << 8) | ((uint32_t)v[4 * i + 2] << 16) |
-                       ((uint32_t)v[4 * i + 3] << 24);
-            else
-                q[i] = (uint32_t)v[2 * i] | ((uint32_t)v[2 * i + 1] << 16);
-        }
-        if constexpr (kBytes == 8) {
-            *reinterpret_cast<uint2 *>(p + s0) = make_uint2(q[0], q[1]);
-        } else {
-#pragma unroll
-            for (int i = 0; i < kBytes / 16; i++)
-                reinterpret_cast<uint4 *>(p + s0)[i] = make_uint4(q[4 * i], q[4 * i + 1], q[4 * i + 2], q[4 * i + 3]);
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < N; k++)
-            if (s0 + k < limit) p[s0 + k] = (Px)v[k];
-    }
-}
-
 // 8 pixels of luma row `row` to R'G'B' samples of type Px (the destination's: the source's own
 // type, or with the colour-volume stage TM the type of dst_bpc)
 template <typename Px, int FMT, bool TM>
@@ -224,8 +194,6 @@ int launch_display_tm(const DisplayArgs &a, const ToneArgs &tm, int bpc, int dst
 }
 
 
-namespace {
-
 // (Kr, Kb) of Dav1dMatrixCoefficients: 0 supported, -ENOTSUP (a matrix that is no Kr / Kb
 // matrix: YCgCo, BT.2020 constant luminance, SMPTE 2085, chromaticity-derived, ICtCp) or -EINVAL
 int matrix_k(int mtrx, double *kr, double *kb) {
@@ -242,8 +210,6 @@ int matrix_k(int mtrx, double *kr, double *kb) {
 }
 
 int round_fix(double v) { return (int)floor(v * (double)(1 << kDispS) + 0.5); }
-
-}  // namespace
 
 int display_check_picture(const MiPicture *in) {
     if (!in->data[0] || in->w <= 0 || in->h <= 0 || in->w > 65536 || in->h > 65536 || in->layout < 0 || in->layout > 3 ||

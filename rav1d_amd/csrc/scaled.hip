@@ -24,6 +24,10 @@
 //                        samples, UV as one vector of 4 interleaved pairs, where the pointer and
 //                        the stride allow, else sample by sample.
 // Luma and chroma of a rung share each launch: the first blocks are luma's.
+//
+// mi_display_scaled_tm is the same call on the tone-mapped picture Q: one launch of yuv_tm.hip's
+// kernel writes Q as planes of dst_bpc into a scratch picture of the context's, after the grain
+// step and in front of the passes, which read it in place of the source.
 #include <algorithm>
 #include <cerrno>
 #include <cstring>
@@ -193,9 +197,14 @@ struct PlaneGeom {
     size_t htab, vtab, mid;   // byte offsets
 };
 
-// mi_display_scaled (rs NULL) and mi_display_scaled_rs
+// the tone map and the target of mi_display_scaled_tm (either may be NULL: it rejects that)
+struct YuvTm { const MiToneMap *tm; const MiYuvTarget *target; };
+
+// mi_display_scaled (rs NULL), mi_display_scaled_rs and, with `yt`, mi_display_scaled_tm: the same
+// passes over the tone-mapped picture Q (yuv_tm.hip), which a kernel in front of them writes into
+// the context's scratch picture
 int display_scaled(MiCtx *ctx, const MiPicture *in, const MiScaledImage *outs, int n_outs, const MiColorInfo *color,
-                   const MiResample *rs, const MiFilmGrainData *fg, void *stream) {
+                   const MiResample *rs, const MiFilmGrainData *fg, void *stream, const YuvTm *yt = nullptr) {
     if (!in || !outs || n_outs < 1 || n_outs > 8) return -EINVAL;
     if (int e = mi::display_check_picture(in)) return e;
     if (int e = mi::display_check_strides(in)) return e;
@@ -232,6 +241,12 @@ int display_scaled(MiCtx *ctx, const MiPicture *in, const MiScaledImage *outs, i
     mi::Filter flt;
     if (int e = mi::resample_check(rs, flt)) return e;
     const int radius = mi::filter_radius(flt);
+    mi::DisplayArgs ya;
+    mi::YuvArgs yf;
+    memset(&ya, 0, sizeof(ya));
+    memset(&yf, 0, sizeof(yf));
+    if (yt)
+        if (int e = mi::yuv_tm_check(in, color, yt->tm, yt->target, ya, yf)) return e;
     if (!ctx) return -EINVAL;
 
     // the scratch: every rung's tables (they stay while the axes stay), then one `mid` the rungs
@@ -269,9 +284,19 @@ int display_scaled(MiCtx *ctx, const MiPicture *in, const MiScaledImage *outs, i
         }
     mi::tap_filter(tl, flt);
     const bool taps = !sc.holds(tl);
+    mi::ToneArgs ta;
+    MiPicture q;
+    if (yt) {
+        if (int e = mi::yuv_tm_scratch(ctx, in, yt->tm->dst_bpc, &q)) return e;
+        if (int e = mi::tone_prepare(ctx, yt->tm, color, in->bpc, (hipStream_t)stream, ta)) return e;
+    }
     MiPicture src = *in;
     if (fg)
         if (int e = mi::display_grain(ctx, in, &src, fg, color, stream)) return e;
+    if (yt) {   // the rungs read Q: the (grained) source through the tone map, at dst_bpc
+        if (mi::yuv_tm_picture(src, color, ya, ta, yf, &q, nullptr, nullptr, q.bpc, (hipStream_t)stream)) return ctx->last_error = -EIO;
+        src = q;
+    }
 
     sc.forget();
     if (taps && mi::launch_taps(tl, (hipStream_t)stream)) return ctx->last_error = -EIO;
@@ -280,8 +305,8 @@ int display_scaled(MiCtx *ctx, const MiPicture *in, const MiScaledImage *outs, i
         mi::ScaledArgs a;
         memset(&a, 0, sizeof(a));
         a.nplanes = nplanes;
-        a.down = o.bpc < in->bpc ? in->bpc - o.bpc : 0;
-        a.up = (o.bpc > in->bpc ? o.bpc - in->bpc : 0) + (o.bpc > 8 ? 16 - o.bpc : 0);
+        a.down = o.bpc < src.bpc ? src.bpc - o.bpc : 0;
+        a.up = (o.bpc > src.bpc ? o.bpc - src.bpc : 0) + (o.bpc > 8 ? 16 - o.bpc : 0);
         a.maxd = (1 << o.bpc) - 1;
         const uintptr_t es = o.bpc == 8 ? 1 : 2;
         for (int p = 0; p < nplanes; p++) {
@@ -306,7 +331,7 @@ int display_scaled(MiCtx *ctx, const MiPicture *in, const MiScaledImage *outs, i
             sp.dstride = o.stride[p];
             sp.dvec = mi::aligned_to(o.data[p], o.stride[p], (p ? 8 : 4) * es);
         }
-        if (mi::launch_scaled(a, in->bpc, o.bpc, (hipStream_t)stream, flt.filter == MI_RS_CUBIC)) return ctx->last_error = -EIO;
+        if (mi::launch_scaled(a, src.bpc, o.bpc, (hipStream_t)stream, flt.filter == MI_RS_CUBIC)) return ctx->last_error = -EIO;
     }
     sc.keep(tl);
     return 0;
@@ -322,4 +347,11 @@ extern "C" int mi_display_scaled(MiCtx *ctx, const MiPicture *in, const MiScaled
 extern "C" int mi_display_scaled_rs(MiCtx *ctx, const MiPicture *in, const MiScaledImage *outs, int n_outs,
                                     const MiColorInfo *color, const MiResample *rs, const MiFilmGrainData *fg, void *stream) {
     return display_scaled(ctx, in, outs, n_outs, color, rs, fg, stream);
+}
+
+extern "C" int mi_display_scaled_tm(MiCtx *ctx, const MiPicture *in, const MiScaledImage *outs, int n_outs,
+                                    const MiColorInfo *color, const MiToneMap *tm, const MiYuvTarget *target,
+                                    const MiResample *rs, const MiFilmGrainData *fg, void *stream) {
+    const YuvTm yt = {tm, target};
+    return display_scaled(ctx, in, outs, n_outs, color, rs, fg, stream, &yt);
 }

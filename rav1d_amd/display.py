@@ -8,7 +8,10 @@ BT.2390 tone curve, primaries conversion, the destination's OETF at a chosen dep
 display_scaled (mi_display_scaled, csrc/scaled.hip) writes cropped, resized semi-planar YUV at a
 chosen depth, several sizes per call: the rungs of a transcode ladder. Both resize with the
 triangle filter, or with resample=Resample(...) (mi_display_tensor_rs / mi_display_scaled_rs) with a
-Mitchell-Netravali cubic: Catmull-Rom, Mitchell, Keys a = -0.75 or any (B, C) in [0, 1]^2."""
+Mitchell-Netravali cubic: Catmull-Rom, Mitchell, Keys a = -0.75 or any (B, C) in [0, 1]^2.
+display_yuv (mi_display_yuv_tm, csrc/yuv_tm.hip) and display_scaled with a ToneMap
+(mi_display_scaled_tm) write the tone-mapped picture as semi-planar YUV in a YuvTarget's matrix and
+range: an HDR10 source as the SDR picture, or the SDR ladder, an encoder takes."""
 import ctypes
 
 import numpy as np
@@ -325,7 +328,41 @@ class ScaledImage:
         return out
 
 
-def display_scaled(ctx, frame, images, color=None, fg=None, stream=None, resample=None):
+class MiYuvTarget(ctypes.Structure):
+    _fields_ = [("mtrx", ctypes.c_int32), ("range", ctypes.c_int32)]
+
+
+def YuvTarget(mtrx=1, range=0):
+    """A MiYuvTarget: the Y'CbCr a tone-mapped YUV output is written in, the matrix (1 BT.709, 4, 5,
+    6 BT.601, 7, 9 BT.2020 NCL) and the range (0 limited, 1 full). The default is what an SDR
+    encoder expects: BT.709, limited."""
+    return MiYuvTarget(int(mtrx), int(range))
+
+
+def output_colour(tonemap, target, chr=0):
+    """The MiColorInfo an encoder should tag the output of display_yuv / display_scaled(tonemap=)
+    with: the tone map's primaries and transfer, the target's matrix and range, the source's chroma
+    siting `chr` (the outputs keep it)."""
+    target = YuvTarget() if target is None else target
+    return MiColorInfo(tonemap.dst_pri, tonemap.dst_trc, target.mtrx, target.range, int(chr))
+
+
+def display_yuv(ctx, frame, image, color, tonemap, target=None, fg=None, stream=None):
+    """Enqueue mi_display_yuv_tm: `frame` (a device Frame or a MiPicture) through the colour-volume
+    stage `tonemap` (a MiToneMap; color.pri, color.trc and color.mtrx describe the source) and back
+    to Y'CbCr in `target` (a MiYuvTarget; None: YuvTarget()), semi-planar at the frame's own
+    subsampling and tonemap.dst_bpc bits, into `image`: a DisplayImage(..., "nv12",
+    out_bpc=tonemap.dst_bpc) or a MiDisplayImage. fg: film grain, applied to the source. Raises
+    MiError on a negative return."""
+    src, cp, fp = _source_args(frame, color, fg)
+    im = image if isinstance(image, MiDisplayImage) else image.image()
+    target = YuvTarget() if target is None else target
+    check(lib().mi_display_yuv_tm(ctx.h, ctypes.byref(src), ctypes.byref(im), cp,
+                                  ctypes.byref(tonemap) if tonemap is not None else None, ctypes.byref(target), fp,
+                                  _stream_ptr(stream)), "mi_display_yuv_tm")
+
+
+def display_scaled(ctx, frame, images, color=None, fg=None, stream=None, resample=None, tonemap=None, target=None):
     """Enqueue mi_display_scaled: `frame` (a device Frame or a MiPicture) cropped, resized and
     converted to each rung's depth into `images`, 1 to 8 ScaledImage or MiScaledImage (or one of
     them on its own), semi-planar at the frame's own subsampling, in one call: film grain (`fg`: a
@@ -333,13 +370,25 @@ def display_scaled(ctx, frame, images, color=None, fg=None, stream=None, resampl
     picture. color: a MiColorInfo or None; only its chr is read (the 4:2:0 chroma siting, of the
     source and of the output). resample: a MiResample (Resample()): the call is
     mi_display_scaled_rs and every plane of every rung is resized with that filter; None calls
-    mi_display_scaled (the triangle). Raises MiError on a negative return."""
+    mi_display_scaled (the triangle). tonemap: a MiToneMap (ToneMap()): the call is
+    mi_display_scaled_tm, the rungs are resized from the tone-mapped picture in the Y'CbCr of
+    `target` (a MiYuvTarget; None: YuvTarget()), color.pri, color.trc and color.mtrx describe the
+    source, and a rung's depth converts from tonemap.dst_bpc (output_colour gives the tags of the
+    result). Without tonemap, `target` must be None. Raises MiError on a negative return."""
     src, cp, fp = _source_args(frame, color, fg)
     if isinstance(images, (ScaledImage, MiScaledImage)):
         images = [images]
     ims = (MiScaledImage * max(len(images), 1))()
     for i, image in enumerate(images):
         ims[i] = image if isinstance(image, MiScaledImage) else image.image()
+    if tonemap is not None:
+        target = YuvTarget() if target is None else target
+        check(lib().mi_display_scaled_tm(ctx.h, ctypes.byref(src), ims, len(images), cp, ctypes.byref(tonemap),
+                                         ctypes.byref(target), ctypes.byref(resample) if resample is not None else None,
+                                         fp, _stream_ptr(stream)), "mi_display_scaled_tm")
+        return
+    if target is not None:
+        raise ValueError("target needs a tonemap: a matrix or range conversion alone is not an output")
     if resample is not None:
         check(lib().mi_display_scaled_rs(ctx.h, ctypes.byref(src), ims, len(images), cp, ctypes.byref(resample), fp,
                                          _stream_ptr(stream)), "mi_display_scaled_rs")
@@ -352,5 +401,5 @@ __all__ = ["DisplayImage", "MiDisplayImage", "MiColorInfo", "display_picture", "
            "MiScaledImage", "ScaledImage", "display_scaled", "even_crop",
            "OUT_SEMIPLANAR", "OUT_RGB_PLANAR", "OUT_RGBA_PACKED",
            "MiTensorImage", "tensor_image", "display_tensor", "T_U8", "T_F16", "T_BF16", "T_F32",
-           "MiToneMap", "ToneMap", "tonemap_tables",
+           "MiToneMap", "ToneMap", "tonemap_tables", "MiYuvTarget", "YuvTarget", "display_yuv", "output_colour",
            "MiResample", "Resample", "RESAMPLE_PRESETS", "RS_TRIANGLE", "RS_CUBIC", "resample_plan", "resample_taps"]

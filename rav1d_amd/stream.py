@@ -221,7 +221,7 @@ def decode_to_batches(ctx, data, size, batch=8, dtype=None, channels_last=False,
 
 def decode_to_ladder(ctx, data, sizes, bpc=None, fit="stretch", apply_grain=True, stream=None, inloop_filters=14,
                      threads=1, operating_point=0, all_layers=True, decode_frame_type="all", frame_size_limit=0,
-                     resample=None):
+                     resample=None, tonemap=None, target=None, primaries=None, transfer=None, matrix=None):
     """Decode a stream on the device and yield, per shown picture in output order, (event, rungs):
     the decoder event that showed it and a list with one (Y, UV) pair of device tensors per entry
     of `sizes` ((W, H) luma sizes), the picture as semi-planar YUV at the stream's own subsampling
@@ -232,7 +232,14 @@ def decode_to_ladder(ctx, data, sizes, bpc=None, fit="stretch", apply_grain=True
     in a stream each get their own crops. Film grain is applied once per picture when the frame
     carries it and apply_grain is set; the chroma siting is the sequence header's. resample: a
     MiResample (rav1d_amd.display.Resample, "mitchell" for instance) for every rung and plane, None
-    the triangle. Every tensor is
+    the triangle. tonemap: a rav1d_amd.display.ToneMap(): the call is mi_display_scaled_tm, every rung
+    is resized from the tone-mapped picture as Y'CbCr in `target` (a rav1d_amd.display.YuvTarget();
+    None: BT.709, limited range), and bpc=None means tonemap.dst_bpc
+    (rav1d_amd.display.output_colour gives the tags of the rungs). primaries, transfer, matrix: the
+    overrides of decode_to_tensors, by its rules: with tonemap, a stream that leaves primaries or
+    transfer unspecified and has no override raises ValueError before any device work of the
+    picture. Without tonemap the overrides are not read and nothing changes (a target on its own is a
+    ValueError: there is no matrix or range conversion without a tone map). Every tensor is
     a fresh allocation the caller owns, filled by work enqueued on `stream` (synchronise it, or
     stay on it, before reading). The other settings are decode_ivf's."""
     from .display import ScaledImage, display_scaled, even_crop
@@ -244,11 +251,15 @@ def decode_to_ladder(ctx, data, sizes, bpc=None, fit="stretch", apply_grain=True
     for ev, src in shown_pictures(ctx, data, stream, threads=threads, inloop_filters=inloop_filters,
                                   operating_point=operating_point, all_layers=all_layers,
                                   decode_frame_type=decode_frame_type, frame_size_limit=frame_size_limit):
-        images = [ScaledImage(W, H, src.bpc if bpc is None else bpc, src.layout,
+        if tonemap is None:
+            color, depth = MiColorInfo(*ev.color.astuple()), src.bpc
+        else:
+            color, depth = _shown_colour(ev, src, matrix, tonemap, primaries, transfer, rgb=True), tonemap.dst_bpc
+        images = [ScaledImage(W, H, depth if bpc is None else bpc, src.layout,
                               even_crop(fit_crop(src.w, src.h, W, H, fit), src.w, src.h, src.layout))
                   for W, H in sizes]
-        display_scaled(ctx, src, images, MiColorInfo(*ev.color.astuple()), _grain(ev, apply_grain), stream,
-                       resample=resample)
+        display_scaled(ctx, src, images, color, _grain(ev, apply_grain), stream, resample=resample, tonemap=tonemap,
+                       target=target)
         yield ev, [im.tensors() for im in images]
 
 

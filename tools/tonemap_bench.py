@@ -15,6 +15,18 @@ size: decoded pictures are smoother. No threshold is asserted; the ratios are re
 
     python tools/tonemap_bench.py [--out profiles/tonemap_bench.json] [--note TEXT]
 
+With --yuv the run measures the tone-mapped YUV outputs instead (mi_display_yuv_tm,
+mi_display_scaled_tm: the same source to 8-bit NV12, BT.709 limited), each row between two takes of
+the existing call it stands beside, into profiles/yuv_tm_bench.json by default:
+
+  rgb8_tm          mi_display_picture_tm, planar R'G'B' at 8 bits: reads what the Q kernel reads;
+  nv12_tm          mi_display_yuv_tm at the source's size;
+  nv12_tm_chr2     the same with co-located chroma (chr 2: the decimation reads the row above too);
+  scaled_1080      plain mi_display_scaled, one 1920 x 1080 8-bit rung (no tone map);
+  scaled_1080_tm   mi_display_scaled_tm, the same rung;
+  ladder           plain mi_display_scaled, 1920 x 1080, 1280 x 720 and 640 x 360 in one call;
+  ladder_tm        mi_display_scaled_tm, the same three rungs.
+
 A variant build of the library (MI_BUILD_VARIANT of rav1d_amd/build.py, loaded with MI_LIB) is
 measured by the same command with another --out; --note says which it was.
 """
@@ -30,7 +42,8 @@ sys.path.insert(0, ROOT)
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "tonemap_bench.json"))
+    ap.add_argument("--out", default=None, help="default: profiles/tonemap_bench.json, with --yuv profiles/yuv_tm_bench.json")
+    ap.add_argument("--yuv", action="store_true", help="measure the tone-mapped YUV outputs and their baselines")
     ap.add_argument("--width", type=int, default=3840)
     ap.add_argument("--height", type=int, default=2160)
     ap.add_argument("--bpc", type=int, default=10)
@@ -40,6 +53,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--note", default="")
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "yuv_tm_bench.json" if args.yuv else "tonemap_bench.json")
 
     import numpy as np
     import torch
@@ -107,6 +122,9 @@ def main():
             us.append(a.elapsed_time(b) * 1e3 / args.iters)
         return float(np.median(us)), [round(v, 2) for v in us]
 
+    if args.yuv:
+        return yuv_rows(args, L, ctx, pic, color, tm8, sp, timed, entry, (w, h, bpc, layout))
+
     results = {}
     order = ["rgba10", "rgba8_tm", "rgba10_tm", "rgba10", "tensor", "tensor_tm", "tensor"]
     for name in order:
@@ -131,6 +149,62 @@ def main():
         f.write("\n")
     print(json.dumps({k: doc[k] for k in ("rgba10_us", "tensor_us", "ratio_rgba8_tm_to_rgba10", "ratio_rgba10_tm_to_rgba10",
                                           "ratio_tensor_tm_to_tensor")}))
+    print("wrote", args.out)
+
+
+def yuv_rows(args, L, ctx, pic, color, tm8, sp, timed, entry, geom):
+    """The --yuv run, on main's source picture, context and timer: the three tone-mapped YUV rows,
+    each between two takes of its baseline."""
+    import torch
+
+    from rav1d_amd import LIB_PATH
+    from rav1d_amd.display import DisplayImage, MiScaledImage, ScaledImage, YuvTarget
+    w, h, bpc, layout = geom
+    ref = ctypes.byref
+    target = YuvTarget(1, 0)
+    color2 = type(color)(color.pri, color.trc, color.mtrx, color.range, 2)
+    rgb8 = DisplayImage(w, h, bpc, layout, "rgb", out_bpc=8)
+    nv12 = DisplayImage(w, h, bpc, layout, "nv12", out_bpc=8)
+    d_rgb8, d_nv12 = rgb8.image(), nv12.image()
+    sizes = [(1920, 1080), (1280, 720), (640, 360)]
+    plain = [ScaledImage(W, H, 8, layout) for W, H in sizes]
+    mapped = [ScaledImage(W, H, 8, layout) for W, H in sizes]
+    ims_plain = (MiScaledImage * 3)(*[im.image() for im in plain])
+    ims_tm = (MiScaledImage * 3)(*[im.image() for im in mapped])
+    cases = {
+        "rgb8_tm": entry(L.mi_display_picture_tm, ctx.h, ref(pic), ref(d_rgb8), ref(color), ref(tm8), None, sp),
+        "nv12_tm": entry(L.mi_display_yuv_tm, ctx.h, ref(pic), ref(d_nv12), ref(color), ref(tm8), ref(target), None, sp),
+        "nv12_tm_chr2": entry(L.mi_display_yuv_tm, ctx.h, ref(pic), ref(d_nv12), ref(color2), ref(tm8), ref(target), None, sp),
+        "scaled_1080": entry(L.mi_display_scaled, ctx.h, ref(pic), ims_plain, 1, ref(color), None, sp),
+        "scaled_1080_tm": entry(L.mi_display_scaled_tm, ctx.h, ref(pic), ims_tm, 1, ref(color), ref(tm8), ref(target), None, None, sp),
+        "ladder": entry(L.mi_display_scaled, ctx.h, ref(pic), ims_plain, 3, ref(color), None, sp),
+        "ladder_tm": entry(L.mi_display_scaled_tm, ctx.h, ref(pic), ims_tm, 3, ref(color), ref(tm8), ref(target), None, None, sp),
+    }
+    results = {}
+    for name in ["rgb8_tm", "nv12_tm", "rgb8_tm", "nv12_tm_chr2", "scaled_1080", "scaled_1080_tm", "scaled_1080", "ladder", "ladder_tm", "ladder"]:
+        us, rounds = timed(cases[name])
+        key = name if name not in results else name + "_again"
+        results[key] = dict(us=round(us, 2), rounds_us=rounds)
+        print(json.dumps({key: results[key]}), flush=True)
+    base = {k: (results[k]["us"] + results[k + "_again"]["us"]) / 2 for k in ("rgb8_tm", "scaled_1080", "ladder")}
+    doc = dict(tool="tools/tonemap_bench.py --yuv", device=torch.cuda.get_device_name(0), library=os.path.basename(LIB_PATH),
+               note=args.note, width=w, height=h, bpc=bpc, layout="4:2:0", rungs=sizes,
+               source="PQ / BT.2020 (pri 9, trc 16, mtrx 9, limited, chr 0), uniformly random codes",
+               tonemap="to sRGB / BT.709 at 8 bits, src_peak 1000, dst_peak 100; target BT.709 limited, NV12",
+               iters=args.iters, warmup=args.warmup, rounds=args.rounds,
+               timing="HIP events around back-to-back calls; median of rounds; each baseline before and after its row",
+               results=results, rgb8_tm_us=round(base["rgb8_tm"], 2), scaled_1080_us=round(base["scaled_1080"], 2),
+               ladder_us=round(base["ladder"], 2),
+               ratio_nv12_tm_to_rgb8_tm=round(results["nv12_tm"]["us"] / base["rgb8_tm"], 3),
+               ratio_nv12_tm_chr2_to_rgb8_tm=round(results["nv12_tm_chr2"]["us"] / base["rgb8_tm"], 3),
+               ratio_scaled_1080_tm_to_scaled_1080=round(results["scaled_1080_tm"]["us"] / base["scaled_1080"], 3),
+               ratio_ladder_tm_to_ladder=round(results["ladder_tm"]["us"] / base["ladder"], 3))
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(doc, f, indent=1)
+        f.write("\n")
+    print(json.dumps({k: doc[k] for k in ("rgb8_tm_us", "scaled_1080_us", "ladder_us", "ratio_nv12_tm_to_rgb8_tm",
+                                          "ratio_scaled_1080_tm_to_scaled_1080", "ratio_ladder_tm_to_ladder")}))
     print("wrote", args.out)
 
 
