@@ -103,6 +103,45 @@ typedef struct MiDecFrame {
     int32_t q_granules;
 } MiDecFrame;
 
+/* HDR metadata OBUs (OBU_METADATA, AV1 5.8; obu.rs, the Rav1dObuType::Metadata arm), as rav1d's
+ * Rav1dContentLightLevel, Rav1dMasteringDisplay and Rav1dITUTT35 carry them with every picture.
+ *
+ * The OBU's payload starts with metadata_type, a leb128:
+ *   1 (HDR CLL): max_cll, max_fall, 16 bits each.
+ *   2 (HDR MDCV): the primaries (x, y) of three colours, 16 bits each (0.16 fixed point), the white
+ *     point (x, y), then max_luminance (24.8 fixed point, cd/m2) and min_luminance (18.14), 32 bits
+ *     each.
+ *   After the fields of either come the trailing one bit and the byte alignment; a payload too
+ *   short for all of that fails mi_dec_send with -EINVAL (check_for_overrun).
+ *   4 (ITU-T T.35): itu_t_t35_country_code, one byte, then country_code_ext when the code is 0xff;
+ *     the payload is every byte after that up to, not including, the last non-zero byte of the
+ *     OBU (the trailing-bit byte 0x80; zero bytes after it are cut with it, zero bytes before it
+ *     belong to the payload). A payload of no bytes is malformed: the OBU is ignored, no error.
+ *     The bytes are delivered, not interpreted (HDR10+, Dolby Vision RPUs: the caller's).
+ *   3 (scalability), 5 (timecode) and every other type are ignored without error.
+ * Lifetime: content light and mastering display stay in force from picture to picture and are
+ * forgotten when a sequence header arrives that differs from the current one (where the
+ * reference slots are dropped too). A T.35 message belongs to the next frame submitted and is
+ * then gone; a second one before that frame replaces the first.
+ * Attachment: a frame takes the state in force when it is submitted (its last tile group has
+ * arrived) and its picture keeps it: the event that shows the picture, a show_existing_frame
+ * event included, reports what that frame took.
+ * Delivery: MiDecEvent itself is unchanged (ABI 4: callers built against it stay binary
+ * compatible); the metadata of an event is read with mi_dec_event_metadata() below, between the
+ * mi_dec_next that returned the event and the next one. */
+typedef struct MiContentLight { int32_t present; uint16_t max_cll, max_fall; } MiContentLight;
+typedef struct MiMasteringDisplay { int32_t present; uint16_t primaries[3][2], white_point[2];
+                                    uint32_t max_luminance, min_luminance; } MiMasteringDisplay;   /* 0.16, 24.8, 18.14 */
+typedef struct MiItutT35 { const uint8_t *payload; int32_t size; uint8_t country_code, country_code_ext; } MiItutT35;
+/* The HDR metadata of the shown picture's frame (show_pic >= 0; else of `frame`) of one event:
+ * present 0 when the frame took none; itut_t35.payload NULL and size 0 without a T.35 message,
+ * else `size` bytes valid until the next mi_dec_next, as release[] is. */
+typedef struct MiDecMetadata {
+    MiContentLight content_light;
+    MiMasteringDisplay mastering_display;
+    MiItutT35 itut_t35;
+} MiDecMetadata;
+
 /* One decoder event: a frame to reconstruct into picture `pic_id` (frame != NULL; its inter
  * prediction reads pictures ref_pic[]), and/or a picture to output (show_pic >= 0, with film
  * grain when fg_present). Pictures listed in release[] are no longer referenced.
@@ -249,6 +288,9 @@ int  mi_dec_drain(MiDec *d);
 int  mi_dec_send(MiDec *d, const uint8_t *data, size_t size);
 /* Next event: 1 and *ev filled, 0 when none is pending, or -errno. */
 int  mi_dec_next(MiDec *d, MiDecEvent *ev);
+/* The HDR metadata (MiDecMetadata above) of the event the last mi_dec_next on `d` returned with 1;
+ * all zero before the first event. 0, or -EINVAL for a NULL argument. */
+int  mi_dec_event_metadata(const MiDec *d, MiDecMetadata *out);
 const char *mi_dec_error(const MiDec *d);
 
 /* What a sequence header says about the pictures to come (Dav1dSequenceHeader's profile,

@@ -231,8 +231,9 @@ int mi_tonemap_tables(const MiToneMap *tm, const MiColorInfo *color, int src_bpc
  * mi_display_picture (its colour-matrix rules included) and of mi_tonemap_tables apply, all before
  * any device work, the NULL `ctx` last. The context owns the device tables: they are rebuilt and
  * uploaded (on `stream`, without synchronising it) only when *tm, color->pri, color->trc or
- * in->bpc differ from the call before; calls on one context use one stream, which orders a table
- * change behind the kernels still reading the old tables. */
+ * in->bpc differ from the call before, and then only the tables that read what changed (a change of
+ * the peaks alone rebuilds lut_in, not the 65536 entries of lut_out); calls on one context use one
+ * stream, which orders a table change behind the kernels still reading the old tables. */
 int mi_display_picture_tm(MiCtx *ctx, const MiPicture *in, const MiDisplayImage *out,
                           const MiColorInfo *color, const MiToneMap *tm,
                           const MiFilmGrainData *fg, void *stream);
@@ -423,6 +424,44 @@ int mi_display_yuv_tm(MiCtx *ctx, const MiPicture *in, const MiDisplayImage *out
 int mi_display_scaled_tm(MiCtx *ctx, const MiPicture *in, const MiScaledImage *outs, int n_outs,
                          const MiColorInfo *color, const MiToneMap *tm, const MiYuvTarget *target,
                          const MiResample *rs, const MiFilmGrainData *fg, void *stream);
+
+/* ---- light level of a picture (librav1d_amd.so) ------------------------------------------- */
+
+/* What src_peak to give the colour-volume stage for a stream that carries no metadata, or whose
+ * container is wider than its content: measured from the decoded planes on the device.
+ *
+ * Let P be the planar R'G'B' picture mi_display_picture writes for `in` and `color` with
+ * MI_OUT_RGB_PLANAR, bpc = in->bpc and no film grain (the chroma upsampler and the 14-bit matrix
+ * stated there). Then
+ *   hist[c] = the number of pixels of P with max(R, G, B) == c, c = 0 .. 2^bpc - 1.
+ * `hist` is device memory of 1 << bpc uint32_t. The entry zeroes it on `stream` and then counts,
+ * never synchronising; the counts are integers, so the result does not depend on the order of
+ * the additions. Film grain is deliberately not applied: it is noise the tone curve should not
+ * follow, and the measurement is cheaper without it. The whole picture is measured (no crop, no
+ * active-area detection).
+ * Every check precedes any device work: -EINVAL for a NULL or malformed `in`, NULL `hist`,
+ * w * h >= 2^32, and the colour rules of mi_display_picture for an RGB format (NULL `color`, mtrx 2
+ * or reserved, a bad range, identity without 4:4:4; -ENOTSUP for matrices 8 and 10-14), the NULL
+ * `ctx` last; -EIO. */
+int mi_picture_light_level(MiCtx *ctx, const MiPicture *in, const MiColorInfo *color, uint32_t *hist, void *stream);
+/* Diagnostic (tools/light_bench.py): the same result through the counting `variant` of
+ * csrc/light.hip (0 one LDS atomic per pixel, 1 equal neighbours of a lane combined, 2 a uniform
+ * wave combined as well: the entry above); -EINVAL for any other. */
+int mi_picture_light_level_variant(MiCtx *ctx, const MiPicture *in, const MiColorInfo *color, uint32_t *hist,
+                                   int variant, void *stream);
+
+/* Host only, no device and no context: the statistics of a histogram of `bpc` bits (8, 10, 12; host
+ * memory of 1 << bpc counts) whose codes are read as full-range PQ (ST 2084: the caller uses it for
+ * trc 16 only). nits(c) = EOTF(c / (2^bpc - 1)) with the EOTF of the colour-volume stage above;
+ * N = sum hist[c].
+ *   max_code: the highest c with hist[c] != 0; max_nits = nits(max_code).
+ *   pct_code: the lowest c with hist[0] + .. + hist[c] >= ceil(percentile / 100 * N), the product in
+ *     double; pct_nits = nits(pct_code).
+ *   avg_nits: sum hist[c] nits(c) / N, summed in double in increasing c: the picture's frame-average
+ *     light level in the CTA-861.3 sense, over the whole picture.
+ * -EINVAL for a NULL argument, a bpc outside the list, a percentile outside (0, 100] and N == 0. */
+typedef struct MiLightLevel { int32_t max_code, pct_code; double max_nits, pct_nits, avg_nits; } MiLightLevel;
+int mi_light_level_stats(const uint32_t *hist, int bpc, double percentile, MiLightLevel *out);
 
 #ifdef __cplusplus
 }

@@ -63,6 +63,32 @@ class MiSeqInfo(ctypes.Structure):
                 ("color", MiColorInfo)]
 
 
+class MiContentLight(ctypes.Structure):
+    """include/mi_av1dec.h: the HDR CLL metadata OBU (Rav1dContentLightLevel), nits."""
+    _fields_ = [("present", ctypes.c_int32), ("max_cll", ctypes.c_uint16), ("max_fall", ctypes.c_uint16)]
+
+
+class MiMasteringDisplay(ctypes.Structure):
+    """include/mi_av1dec.h: the HDR MDCV metadata OBU (Rav1dMasteringDisplay): chromaticities in
+    0.16 fixed point, max_luminance in 24.8, min_luminance in 18.14."""
+    _fields_ = [("present", ctypes.c_int32), ("primaries", (ctypes.c_uint16 * 2) * 3),
+                ("white_point", ctypes.c_uint16 * 2),
+                ("max_luminance", ctypes.c_uint32), ("min_luminance", ctypes.c_uint32)]
+
+
+class MiItutT35(ctypes.Structure):
+    """include/mi_av1dec.h: an ITU-T T.35 metadata OBU (Rav1dITUTT35); payload is valid until the
+    next event (MiDecEvent.t35_payload is the copy)."""
+    _fields_ = [("payload", ctypes.c_void_p), ("size", ctypes.c_int32),
+                ("country_code", ctypes.c_uint8), ("country_code_ext", ctypes.c_uint8)]
+
+
+class MiDecMetadata(ctypes.Structure):
+    """include/mi_av1dec.h: what mi_dec_event_metadata reports for an event."""
+    _fields_ = [("content_light", MiContentLight), ("mastering_display", MiMasteringDisplay),
+                ("itut_t35", MiItutT35)]
+
+
 class MiDecEvent(ctypes.Structure):
     _fields_ = [("frame", ctypes.POINTER(MiDecFrame)), ("pic_id", ctypes.c_int32),
                 ("ref_pic", ctypes.c_int32 * 7), ("show_pic", ctypes.c_int32),
@@ -71,6 +97,11 @@ class MiDecEvent(ctypes.Structure):
                 ("mtrx_identity", ctypes.c_int32),
                 ("temporal_id", ctypes.c_int32), ("spatial_id", ctypes.c_int32),
                 ("new_temporal_unit", ctypes.c_int32), ("color", MiColorInfo)]
+    # The struct is the header's (ABI 4). Av1Decoder.events() adds, per event, what
+    # mi_dec_event_metadata reports for it, as plain attributes: content_light (MiContentLight),
+    # mastering_display (MiMasteringDisplay), itut_t35 (MiItutT35) and t35_payload, the T.35
+    # message as bytes (a copy). None on an event that did not come from a decoder.
+    content_light = mastering_display = itut_t35 = t35_payload = None
 
 
 def build_dec():
@@ -88,6 +119,7 @@ def dec_lib():
         d.mi_dec_destroy.restype = None
         d.mi_dec_send.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t]
         d.mi_dec_next.argtypes = [ctypes.c_void_p, ctypes.POINTER(MiDecEvent)]
+        d.mi_dec_event_metadata.argtypes = [ctypes.c_void_p, ctypes.POINTER(MiDecMetadata)]
         d.mi_dec_set_threads.argtypes = [ctypes.c_void_p, ctypes.c_int]
         d.mi_dec_set_inloop_filters.argtypes = [ctypes.c_void_p, ctypes.c_int]
         d.mi_dec_set_operating_point.argtypes = [ctypes.c_void_p, ctypes.c_int]
@@ -289,7 +321,10 @@ class Av1Decoder:
             raise DecoderError("mi_dec_drain", r, self.error())
 
     def events(self):
-        """Yield MiDecEvent structs; each is valid only until the next one is requested."""
+        """Yield MiDecEvent structs; each is valid only until the next one is requested. Every event
+        carries its HDR metadata (mi_dec_event_metadata) as the attributes content_light,
+        mastering_display and itut_t35, and t35_payload: the ITU-T T.35 message of the event's frame
+        as bytes (a copy the caller may keep), or None."""
         ev = MiDecEvent()
         while True:
             r = self.lib.mi_dec_next(self.h, ctypes.byref(ev))
@@ -297,6 +332,13 @@ class Av1Decoder:
                 raise DecoderError("mi_dec_next", r, self.error())
             if r == 0:
                 return
+            md = MiDecMetadata()
+            r = self.lib.mi_dec_event_metadata(self.h, ctypes.byref(md))
+            if r < 0:
+                raise DecoderError("mi_dec_event_metadata", r, self.error())
+            ev.content_light, ev.mastering_display, ev.itut_t35 = md.content_light, md.mastering_display, md.itut_t35
+            t = md.itut_t35
+            ev.t35_payload = ctypes.string_at(t.payload, t.size) if t.payload and t.size > 0 else None
             yield ev
 
 

@@ -76,7 +76,9 @@ struct MiCtx {
     MiResizeScratch tens, scal;
     // mi_display_*_tm: the device tables (lut_out, then lut_in) of the key `tone_key` (*tm with
     // the peaks zeroed for sources that do not read them, pri, trc, source bpc), their matrix, and
-    // two pinned staging buffers used in turn; `tone_ev[i]` marks when buffer i may be rewritten
+    // two pinned staging buffers used in turn; `tone_ev[i]` marks when buffer i may be rewritten.
+    // tone_prepare compares the key per table (lut_out: dst_trc, dst_bpc; lut_in: peaks, trc,
+    // source bpc; m: the primaries) and rebuilds only the stale ones
     uint8_t *tone_dev = nullptr;
     uint8_t *tone_host[2] = {nullptr, nullptr};
     hipEvent_t tone_ev[2] = {nullptr, nullptr};

@@ -113,12 +113,12 @@ void invert3(const double (&a)[3][3], double (&o)[3][3]) {
         }
 }
 
-// all three tables; every argument checked before
-void tone_tables(const MiToneMap &tm, int pri, int trc, int src_bpc, float *lut_in, float *m, uint16_t *lut_out) {
+// the three tables, each from what it depends on alone; every argument checked before
+void tone_table_in(const MiToneMap &tm, int trc, int src_bpc, float *lut_in) {
     int curve = kCurve709;
     (void)trc_class(trc, &curve);
     const int n = 1 << src_bpc;
-    const double ms = (double)(n - 1), md = (double)((1 << tm.dst_bpc) - 1);
+    const double ms = (double)(n - 1);
     // (the running maximum: the BT.709 curve's two segments, with the constants as rounded in the
     // standard, meet 5.5e-5 apart at x = 0.081, which at 12 bits is more than one code's step)
     double top = 0.0;
@@ -127,17 +127,30 @@ void tone_tables(const MiToneMap &tm, int pri, int trc, int src_bpc, float *lut_
         const float f = (float)top;
         lut_in[v] = std::fpclassify(f) == FP_SUBNORMAL ? 0.0f : f;
     }
-    if (pri == tm.dst_pri) {
+}
+
+void tone_table_m(int dst_pri, int pri, float *m) {
+    if (pri == dst_pri) {
         for (int i = 0; i < 9; i++) m[i] = i % 4 == 0 ? 1.0f : 0.0f;
     } else {
         double s[3][3], d[3][3], di[3][3];
         rgb_to_xyz(pri, s);
-        rgb_to_xyz(tm.dst_pri, d);
+        rgb_to_xyz(dst_pri, d);
         invert3(d, di);
         for (int r = 0; r < 3; r++)
             for (int c = 0; c < 3; c++) m[3 * r + c] = (float)(di[r][0] * s[0][c] + di[r][1] * s[1][c] + di[r][2] * s[2][c]);
     }
-    for (int i = 0; i < kOutN; i++) lut_out[i] = (uint16_t)floor(oetf(tm.dst_trc, (double)i / 65535.0) * md + 0.5);
+}
+
+void tone_table_out(int dst_trc, int dst_bpc, uint16_t *lut_out) {
+    const double md = (double)((1 << dst_bpc) - 1);
+    for (int i = 0; i < kOutN; i++) lut_out[i] = (uint16_t)floor(oetf(dst_trc, (double)i / 65535.0) * md + 0.5);
+}
+
+void tone_tables(const MiToneMap &tm, int pri, int trc, int src_bpc, float *lut_in, float *m, uint16_t *lut_out) {
+    tone_table_in(tm, trc, src_bpc, lut_in);
+    tone_table_m(tm.dst_pri, pri, m);
+    tone_table_out(tm.dst_trc, tm.dst_bpc, lut_out);
 }
 
 }  // namespace
@@ -172,7 +185,14 @@ int tone_prepare(MiCtx *ctx, const MiToneMap *tm, const MiColorInfo *color, int 
             return ctx->last_error = -ENOMEM;
         }
     }
-    if (!ctx->tone_valid || memcmp(key, ctx->tone_key, sizeof(key)) != 0) {
+    // What each table depends on: lut_out on (dst_trc, dst_bpc), lut_in on the peaks, the source
+    // trc and depth, m on the two primaries. A change of peaks alone (a caller that follows the
+    // stream's light level) rebuilds and uploads lut_in only: lut_out is 65536 pow() and 128 KB.
+    const int32_t *old = ctx->tone_key;
+    const bool out_stale = !ctx->tone_valid || key[1] != old[1] || key[2] != old[2];
+    const bool in_stale = !ctx->tone_valid || key[3] != old[3] || key[4] != old[4] || key[6] != old[6] || key[7] != old[7];
+    const bool m_stale = !ctx->tone_valid || key[0] != old[0] || key[5] != old[5];
+    if (out_stale || in_stale) {
         // Build into the staging buffer whose turn it is. The upload before the last one read it;
         // wait for that one only if it is still pending (two buffers: a change of tables behind
         // another does not wait for the stream).
@@ -193,9 +213,13 @@ int tone_prepare(MiCtx *ctx, const MiToneMap *tm, const MiColorInfo *color, int 
         }
         uint8_t *h = ctx->tone_host[i];
         ctx->tone_valid = false;
-        tone_tables(k, color->pri, color->trc, src_bpc, (float *)(h + out_bytes), ctx->tone_m, (uint16_t *)h);
-        const size_t bytes = out_bytes + ((size_t)sizeof(float) << src_bpc);
-        if (hipMemcpyAsync(ctx->tone_dev, h, bytes, hipMemcpyHostToDevice, s) != hipSuccess) return ctx->last_error = -EIO;
+        if (out_stale) tone_table_out(k.dst_trc, k.dst_bpc, (uint16_t *)h);
+        if (in_stale) tone_table_in(k, color->trc, src_bpc, (float *)(h + out_bytes));
+        // (the tables are adjacent, on the host as on the device: one copy of what changed)
+        const size_t from = out_stale ? 0 : out_bytes;
+        const size_t to = in_stale ? out_bytes + ((size_t)sizeof(float) << src_bpc) : out_bytes;
+        if (hipMemcpyAsync(ctx->tone_dev + from, h + from, to - from, hipMemcpyHostToDevice, s) != hipSuccess)
+            return ctx->last_error = -EIO;
         if (hipEventRecord(ctx->tone_ev[i], s) != hipSuccess) {
             // without the event the buffer's reuse cannot be ordered: let the upload finish now
             (void)hipStreamSynchronize(s);
@@ -203,9 +227,10 @@ int tone_prepare(MiCtx *ctx, const MiToneMap *tm, const MiColorInfo *color, int 
             ctx->tone_ev_pending[i] = true;
         }
         ctx->tone_slot = i ^ 1;
-        memcpy(ctx->tone_key, key, sizeof(key));
-        ctx->tone_valid = true;
     }
+    if (m_stale) tone_table_m(k.dst_pri, color->pri, ctx->tone_m);
+    memcpy(ctx->tone_key, key, sizeof(key));
+    ctx->tone_valid = true;
     t.lut_out = (const uint16_t *)ctx->tone_dev;
     t.lut_in = (const float *)(ctx->tone_dev + out_bytes);
     memcpy(t.m, ctx->tone_m, sizeof(t.m));
@@ -221,5 +246,40 @@ extern "C" int mi_tonemap_tables(const MiToneMap *tm, const MiColorInfo *color, 
     if (!lut_in || !m || !lut_out || (src_bpc != 8 && src_bpc != 10 && src_bpc != 12)) return -EINVAL;
     if (int e = mi::tone_check(tm, color)) return e;
     mi::tone_tables(*tm, color->pri, color->trc, src_bpc, lut_in, m, lut_out);
+    return 0;
+}
+
+extern "C" int mi_light_level_stats(const uint32_t *hist, int bpc, double percentile, MiLightLevel *out) {
+    if (!hist || !out || (bpc != 8 && bpc != 10 && bpc != 12)) return -EINVAL;
+    if (!(percentile > 0.0 && percentile <= 100.0)) return -EINVAL;
+    const int n = 1 << bpc;
+    uint64_t total = 0;
+    for (int c = 0; c < n; c++) total += hist[c];
+    if (!total) return -EINVAL;
+    const double want = ceil(percentile / 100.0 * (double)total), top = (double)(n - 1);
+    uint64_t cum = 0;
+    int max_code = 0, pct_code = -1;
+    double sum = 0.0, max_nits = 0.0, pct_nits = 0.0;
+    for (int c = 0; c < n; c++) {
+        if (!hist[c]) continue;
+        const double nits = mi::pq_eotf((double)c / top);
+        cum += hist[c];
+        sum += (double)hist[c] * nits;
+        max_code = c;
+        max_nits = nits;
+        if (pct_code < 0 && (double)cum >= want) {
+            pct_code = c;
+            pct_nits = nits;
+        }
+    }
+    if (pct_code < 0) {   // (the product rounded above N: the last pixel it is)
+        pct_code = max_code;
+        pct_nits = max_nits;
+    }
+    out->max_code = max_code;
+    out->pct_code = pct_code;
+    out->max_nits = max_nits;
+    out->pct_nits = pct_nits;
+    out->avg_nits = sum / (double)total;
     return 0;
 }

@@ -397,9 +397,71 @@ def display_scaled(ctx, frame, images, color=None, fg=None, stream=None, resampl
           "mi_display_scaled")
 
 
+class MiLightLevel(ctypes.Structure):
+    _fields_ = [("max_code", ctypes.c_int32), ("pct_code", ctypes.c_int32),
+                ("max_nits", ctypes.c_double), ("pct_nits", ctypes.c_double), ("avg_nits", ctypes.c_double)]
+
+
+_light = None
+
+
+def _light_lib():
+    """lib() with the signatures of the light-level entries set (a library without them raises
+    AttributeError here: nothing stands in for a missing entry)."""
+    global _light
+    if _light is None:
+        L, vp = lib(), ctypes.c_void_p
+        for name, args in (("mi_picture_light_level", [vp, ctypes.POINTER(MiPicture), vp, vp, vp]),
+                           ("mi_picture_light_level_variant", [vp, ctypes.POINTER(MiPicture), vp, vp, ctypes.c_int, vp]),
+                           ("mi_light_level_stats", [vp, ctypes.c_int, ctypes.c_double, vp])):
+            f = getattr(L, name)
+            f.restype, f.argtypes = ctypes.c_int, args
+        _light = L
+    return _light
+
+
+def light_level(ctx, frame, color, stream=None, variant=None):
+    """Enqueue mi_picture_light_level: the histogram of max(R', G', B') over the planar R'G'B'
+    picture display_picture(..., "rgb") would write for `frame` (a device Frame or a MiPicture)
+    and `color`, without film grain. Returns a fresh torch.int32 device tensor of 1 << bpc bins
+    (the bits are those of the uint32 counts), filled by work enqueued on `stream`. variant: the
+    counting variant of mi_picture_light_level_variant (a diagnostic; None: the entry itself).
+    Raises MiError on a negative return."""
+    src = frame if isinstance(frame, MiPicture) else frame.picture()
+    n = 1 << src.bpc if src.bpc in (8, 10, 12) else 1
+    hist = torch.empty(n, dtype=torch.int32, device="cuda")
+    cp = ctypes.byref(color) if color is not None else None
+    if variant is None:
+        check(_light_lib().mi_picture_light_level(ctx.h, ctypes.byref(src), cp, ctypes.c_void_p(hist.data_ptr()),
+                                           _stream_ptr(stream)), "mi_picture_light_level")
+    else:
+        check(_light_lib().mi_picture_light_level_variant(ctx.h, ctypes.byref(src), cp, ctypes.c_void_p(hist.data_ptr()),
+                                                   int(variant), _stream_ptr(stream)), "mi_picture_light_level_variant")
+    return hist
+
+
+def light_stats(hist, bpc, percentile=99.99):
+    """mi_light_level_stats (host only): the MiLightLevel of a histogram of `bpc` bits read as
+    full-range PQ codes: max_code / max_nits, pct_code / pct_nits (the lowest code whose
+    cumulative count reaches ceil(percentile / 100 * N)) and avg_nits. hist: light_level's tensor
+    (copied to the host, which synchronises) or any array of 1 << bpc counts. Raises MiError on a
+    negative return (an empty histogram, a percentile outside (0, 100])."""
+    if isinstance(hist, torch.Tensor):
+        hist = hist.cpu().numpy()
+    h = np.ascontiguousarray(np.asarray(hist).view(np.uint32) if np.asarray(hist).dtype == np.int32
+                             else np.asarray(hist, dtype=np.uint32))
+    if bpc in (8, 10, 12) and h.size != 1 << bpc:
+        raise ValueError(f"hist of {h.size} bins for {bpc} bits")
+    out = MiLightLevel()
+    check(_light_lib().mi_light_level_stats(h.ctypes.data_as(ctypes.c_void_p), int(bpc), ctypes.c_double(percentile),
+                                     ctypes.byref(out)), "mi_light_level_stats")
+    return out
+
+
 __all__ = ["DisplayImage", "MiDisplayImage", "MiColorInfo", "display_picture", "FORMATS",
            "MiScaledImage", "ScaledImage", "display_scaled", "even_crop",
            "OUT_SEMIPLANAR", "OUT_RGB_PLANAR", "OUT_RGBA_PACKED",
            "MiTensorImage", "tensor_image", "display_tensor", "T_U8", "T_F16", "T_BF16", "T_F32",
            "MiToneMap", "ToneMap", "tonemap_tables", "MiYuvTarget", "YuvTarget", "display_yuv", "output_colour",
+           "MiLightLevel", "light_level", "light_stats",
            "MiResample", "Resample", "RESAMPLE_PRESETS", "RS_TRIANGLE", "RS_CUBIC", "resample_plan", "resample_taps"]

@@ -12,6 +12,7 @@ struct MiDec {
     std::vector<int32_t> release;
     std::string err;
     int inloop = MI_INLOOPFILTER_ALL;
+    bool has_cur = false;   // `cur` is an event mi_dec_next returned
 };
 
 extern "C" {
@@ -102,9 +103,11 @@ int mi_dec_next(MiDec *d, MiDecEvent *ev) {
         return -EAGAIN;
     }
     if (r <= 0) {
+        if (r < 0) d->has_cur = false;   // (`cur` is the frame that failed)
         if (r < 0 && d->dec.error.find("not supported") != std::string::npos) return -ENOTSUP;
         return r;
     }
+    d->has_cur = true;
     const av1::DecEvent &e = d->cur;
     memset(ev, 0, sizeof(*ev));
     ev->pic_id = e.pic_id;
@@ -130,6 +133,22 @@ int mi_dec_next(MiDec *d, MiDecEvent *ev) {
         ev->frame = &f;
     }
     return 1;
+}
+
+int mi_dec_event_metadata(const MiDec *d, MiDecMetadata *out) {
+    if (!d || !out) return -EINVAL;
+    memset(out, 0, sizeof(*out));
+    if (!d->has_cur) return 0;
+    const av1::FrameMeta &m = d->cur.meta;
+    out->content_light = m.cll;
+    out->mastering_display = m.mdcv;
+    if (m.t35) {   // (d->cur keeps the bytes until the next mi_dec_next)
+        out->itut_t35.payload = m.t35->payload.data();
+        out->itut_t35.size = (int32_t)m.t35->payload.size();
+        out->itut_t35.country_code = m.t35->country_code;
+        out->itut_t35.country_code_ext = m.t35->country_code_ext;
+    }
+    return 0;
 }
 
 int mi_dec_parse_sequence_header(const uint8_t *data, size_t size, MiSeqInfo *out) {

@@ -21,6 +21,18 @@ struct FrameJob;
 
 inline MiColorInfo color_info(const SeqHdr &s) { return MiColorInfo{s.pri, s.trc, s.mtrx, s.color_range, s.chr}; }
 
+// The HDR metadata a frame took when it was submitted (include/mi_av1dec.h): rav1d's
+// Rav1dPicture.content_light / mastering_display / itut_t35.
+struct ItutT35 {
+    uint8_t country_code = 0, country_code_ext = 0;
+    std::vector<uint8_t> payload;
+};
+struct FrameMeta {
+    MiContentLight cll{};
+    MiMasteringDisplay mdcv{};
+    std::shared_ptr<const ItutT35> t35;
+};
+
 struct RefSlot {
     int pic_id = -1;
     // set while the frame that refreshed this slot is still being decoded on a worker thread:
@@ -35,6 +47,7 @@ struct RefSlot {
     int bw, bh;   // 4x4-unit frame size the segmap / mvs belong to
     int showable;
     int new_tu = 0;   // the frame was the first its temporal unit decoded (PICTURE_FLAG_NEW_TEMPORAL_UNIT)
+    FrameMeta meta;   // what the frame took (a show_existing_frame reports it)
 };
 
 // One entry of the decoder's output queue: a frame to reconstruct (work != null) and/or a
@@ -53,6 +66,7 @@ struct DecEvent {
     // that frame was the first its temporal unit decoded
     int temporal_id = 0, spatial_id = 0, new_tu = 0;
     MiColorInfo color{};             // colour description of that frame's sequence header
+    FrameMeta meta;                  // HDR metadata of that frame
 };
 
 // A picture on its way out (c.out / c.cache of the reference: src/lib.rs output_picture_ready).
@@ -62,6 +76,7 @@ struct ShownPic {
     int fg_present = 0, mtrx_identity = 0;
     int temporal_id = 0, spatial_id = 0, new_tu = 0;
     MiColorInfo color{};
+    FrameMeta meta;
 };
 
 class Decoder {
@@ -91,6 +106,7 @@ public:
 
 private:
     int parse_obu(const uint8_t *data, size_t size, size_t *used);
+    int parse_metadata(const uint8_t *obu, size_t len);
     static int parse_seq_hdr(Bits &gb, SeqHdr &s);
     int parse_frame_hdr(Bits &gb, FrameHdr &h);
     int read_frame_size(Bits &gb, FrameHdr &h, bool use_ref);
@@ -121,6 +137,11 @@ private:
     int max_spatial_id_ = 0;    // its highest spatial layer
     int new_tu_ = 0;            // a temporal delimiter was seen since the last frame decoded
     ShownPic cache_;            // the shown picture held back (all_layers == false); pic < 0: none
+    // metadata OBUs: content light and mastering display in force (cleared by a new sequence),
+    // and the T.35 message waiting for the next frame submitted
+    MiContentLight cll_{};
+    MiMasteringDisplay mdcv_{};
+    std::shared_ptr<const ItutT35> t35_;
 };
 
 // What a frame decoding on a worker makes available to the frames that reference it before it

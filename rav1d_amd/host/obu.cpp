@@ -782,6 +782,8 @@ int Decoder::parse_obu(const uint8_t *data, size_t size, size_t *used) {
         for (int m = op_idc_ >> 8; m > 1; m >>= 1) max_spatial_id_++;
         if (seq_ && memcmp(s.get(), seq_.get(), sizeof(SeqHdr))) {
             // a new sequence: forget everything decoded under the old one
+            cll_ = MiContentLight{};
+            mdcv_ = MiMasteringDisplay{};
             int old_ids[8];
             for (int i = 0; i < 8; i++) old_ids[i] = refs_[i].pic_id;
             for (auto &rs : refs_) rs = RefSlot();
@@ -843,6 +845,7 @@ int Decoder::parse_obu(const uint8_t *data, size_t size, size_t *used) {
             sp.temporal_id = rs.hdr->temporal_id;
             sp.spatial_id = rs.hdr->spatial_id;
             sp.new_tu = rs.new_tu;
+            sp.meta = rs.meta;
             const int ended = show(ev, sp);
             if (rs.hdr->frame_type == FRAME_KEY) {
                 // a shown key frame refreshes every slot (obu.rs show_existing_frame)
@@ -908,7 +911,15 @@ int Decoder::parse_obu(const uint8_t *data, size_t size, size_t *used) {
     case 2:   // temporal delimiter: the next frame decoded starts a temporal unit
         new_tu_ = 1;
         break;
-    default:   // metadata, padding, tile list: nothing for the pixels
+    case 5: {   // metadata
+        const int r = parse_metadata(obu, len);
+        if (r < 0) {
+            error = "bad metadata OBU";
+            return r;
+        }
+        break;
+    }
+    default:   // padding, tile list: nothing for the pixels
         break;
     }
     if (frame_hdr_ && !frame_hdr_->show_existing_frame &&
@@ -926,6 +937,69 @@ int Decoder::parse_obu(const uint8_t *data, size_t size, size_t *used) {
         tiles_.clear();
         n_tiles_ = 0;
         if (r < 0) return r;
+    }
+    return 0;
+}
+
+// A metadata OBU's payload (obu.rs, the Rav1dObuType::Metadata arm): HDR CLL and MDCV replace the
+// state in force, a T.35 message waits for the next frame submitted; scalability, timecode and
+// unknown types are skipped. -EINVAL when a CLL / MDCV payload ends before its trailing bit
+// (check_for_overrun).
+int Decoder::parse_metadata(const uint8_t *obu, size_t len) {
+    Bits b;
+    b.init(obu, len);
+    const unsigned type = b.uleb128();
+    if (b.error) return -EINVAL;
+    const int type_len = (int)b.byte_pos();
+    switch (type) {
+    case 1: {   // HDR CLL
+        MiContentLight c{};
+        c.present = 1;
+        c.max_cll = (uint16_t)b.bits(16);
+        c.max_fall = (uint16_t)b.bits(16);
+        b.bit();   // trailing one bit
+        b.byte_align();
+        if (b.error || b.pos > 8 * len) return -EINVAL;
+        cll_ = c;
+        break;
+    }
+    case 2: {   // HDR MDCV
+        MiMasteringDisplay m{};
+        m.present = 1;
+        for (int i = 0; i < 3; i++) {
+            m.primaries[i][0] = (uint16_t)b.bits(16);
+            m.primaries[i][1] = (uint16_t)b.bits(16);
+        }
+        m.white_point[0] = (uint16_t)b.bits(16);
+        m.white_point[1] = (uint16_t)b.bits(16);
+        m.max_luminance = b.bits(32);
+        m.min_luminance = b.bits(32);
+        b.bit();
+        b.byte_align();
+        if (b.error || b.pos > 8 * len) return -EINVAL;
+        mdcv_ = m;
+        break;
+    }
+    case 4: {   // ITU-T T.35
+        // the payload ends before the trailing-bit byte: the OBU's last non-zero byte
+        int64_t n = (int64_t)len;
+        while (n > 0 && obu[n - 1] == 0) n--;
+        n -= 1 + type_len;
+        auto t = std::make_shared<ItutT35>();
+        t->country_code = (uint8_t)b.bits(8);
+        n--;
+        if (t->country_code == 0xff) {
+            t->country_code_ext = (uint8_t)b.bits(8);
+            n--;
+        }
+        if (n <= 0) break;   // malformed: ignored
+        const size_t off = b.byte_pos();
+        t->payload.assign(obu + off, obu + off + n);
+        t35_ = std::move(t);
+        break;
+    }
+    default:   // scalability (3), timecode (5), unknown
+        break;
     }
     return 0;
 }
@@ -959,6 +1033,7 @@ static void put(DecEvent &ev, const ShownPic &s) {
     ev.temporal_id = s.temporal_id;
     ev.spatial_id = s.spatial_id;
     ev.new_tu = s.new_tu;
+    ev.meta = s.meta;
 }
 
 // A shown picture on its way out (src/lib.rs:391-438 output_picture_ready / output_image, one
@@ -1295,6 +1370,12 @@ int Decoder::submit_frame() {
     ev.spatial_id = h.spatial_id;
     ev.new_tu = new_tu;
     ev.color = color_info(s);
+    // the metadata in force goes with the frame; the T.35 message is its alone (c.itut_t35.take())
+    ev.meta.cll = cll_;
+    ev.meta.mdcv = mdcv_;
+    ev.meta.t35 = std::move(t35_);
+    t35_.reset();
+    const FrameMeta meta = ev.meta;
     int ended = -1;
     if (h.show_frame) {
         ShownPic sp;
@@ -1306,6 +1387,7 @@ int Decoder::submit_frame() {
         sp.temporal_id = h.temporal_id;
         sp.spatial_id = h.spatial_id;
         sp.new_tu = new_tu;
+        sp.meta = meta;
         ended = show(ev, sp);
     }
     // reference slots (decode.rs submit_frame: refresh_frame_flags)
@@ -1342,6 +1424,7 @@ int Decoder::submit_frame() {
         rs.bh = bh;
         rs.showable = h.showable_frame;
         rs.new_tu = new_tu;
+        rs.meta = meta;
     }
     release_unused(ev, old_ids);
     end_hold(ev, ended);

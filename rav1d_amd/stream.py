@@ -122,9 +122,77 @@ def _source_colour(color, tonemap, primaries, transfer):
                          f"trc {color.trc} (2: unspecified); pass primaries= / transfer=")
 
 
+class PeakTracker:
+    """The smoothing of peak="measured": per picture, update(m) takes the measured light level m
+    (nits) and returns the src_peak to map that picture with. The state s follows m at once
+    upwards and by a sixteenth of the distance downwards (s = m if m >= s else s + (m - s) / 16,
+    in float64; the first m sets it), the result is s raised to a multiple of 100 nits and clamped
+    to [max(100, dst_peak), 10000]. The quantum keeps the result, and so the device tables, the
+    same from picture to picture within a scene. No GPU is involved."""
+
+    QUANTUM, RELEASE = 100.0, 16.0
+
+    def __init__(self, dst_peak=100.0):
+        self.lo = max(100.0, float(dst_peak))
+        self.s = None
+
+    def update(self, m):
+        import math
+        m = float(m)
+        self.s = m if self.s is None or m >= self.s else self.s + (m - self.s) / self.RELEASE
+        q = math.ceil(self.s / self.QUANTUM) * self.QUANTUM
+        return min(max(q, self.lo), 10000.0)
+
+
+def metadata_peak(ev, tonemap):
+    """The src_peak peak="metadata" takes from a decoder event: the mastering display's
+    max_luminance / 256 (24.8 fixed point) when the event has one with max_luminance > 0, else
+    max_cll when content light is present and > 0, else the tone map's own src_peak. Not clamped
+    (_with_peak does that)."""
+    md, cl = ev.mastering_display, ev.content_light      # (None: an event without metadata attached)
+    if md is not None and md.present and md.max_luminance > 0:
+        return md.max_luminance / 256.0
+    if cl is not None and cl.present and cl.max_cll > 0:
+        return float(cl.max_cll)
+    return float(tonemap.src_peak)
+
+
+PEAK_MODES = (None, "metadata", "measured")
+
+
+def _check_peak(peak, tonemap):
+    if peak not in PEAK_MODES:
+        raise ValueError(f"peak {peak!r}: want None, 'metadata' or 'measured'")
+    if peak is not None and tonemap is None:
+        raise ValueError("peak needs a tonemap: it chooses the tone map's src_peak")
+
+
+def _with_peak(tonemap, nits):
+    """A copy of `tonemap` with src_peak = nits clamped to [dst_peak, 10000] (the stage wants
+    peaks in [1, 10000]; a source peak below the target's has nothing to compress)."""
+    from .display import MiToneMap
+    lo = max(1.0, float(tonemap.dst_peak))
+    return MiToneMap(tonemap.dst_pri, tonemap.dst_trc, tonemap.dst_bpc, min(max(float(nits), lo), 10000.0),
+                     tonemap.dst_peak)
+
+
+def _picture_tonemap(ctx, ev, src, color, tonemap, peak, tracker, stream):
+    """The tone map a shown picture's output call gets: `tonemap` itself for peak=None, else a copy
+    whose src_peak comes from the event's metadata or from the picture (light_level, then
+    light_stats: a synchronisation per picture, the stated cost of "measured")."""
+    if peak is None:
+        return tonemap
+    if color.trc != 16:
+        raise ValueError(f"peak={peak!r} needs a PQ source (trc 16): the picture has trc {color.trc}")
+    if peak == "metadata":
+        return _with_peak(tonemap, metadata_peak(ev, tonemap))
+    from .display import light_level, light_stats
+    return _with_peak(tonemap, tracker.update(light_stats(light_level(ctx, src, color, stream), src.bpc, 99.99).pct_nits))
+
+
 def decode_to_tensors(ctx, data, format="nv12", apply_grain=True, matrix=None, stream=None, inloop_filters=14,
                       threads=1, operating_point=0, all_layers=True, decode_frame_type="all", frame_size_limit=0,
-                      tonemap=None, primaries=None, transfer=None):
+                      tonemap=None, primaries=None, transfer=None, peak=None):
     """Decode a stream (IVF, Annex B or section 5) on the device and yield, per shown picture in
     output order, (DisplayImage, MiColorInfo): the picture as a tight device tensor in `format`
     ("nv12": semi-planar at the stream's own subsampling and bit depth; "rgb": planar R'G'B';
@@ -144,17 +212,27 @@ def decode_to_tensors(ctx, data, format="nv12", apply_grain=True, matrix=None, s
     the image holds samples of tonemap.dst_bpc bits in the tone map's primaries and transfer.
     primaries, transfer: Dav1dColorPrimaries / Dav1dTransferCharacteristics values that override
     the stream's (as matrix does; the MiColorInfo yielded carries them). With tonemap, a stream
-    that leaves either unspecified and has no override raises ValueError. The other settings are
-    decode_ivf's."""
+    that leaves either unspecified and has no override raises ValueError.
+
+    peak: where a PQ source's src_peak comes from (read with tonemap only, and for a source whose
+    trc after the overrides is 16: a ValueError otherwise when it is not None). None: the tone
+    map's own. "metadata": per shown picture, the stream's mastering display or content light
+    (metadata_peak). "measured": per shown picture, the 99.99th percentile of max(R', G', B') of
+    the picture itself (rav1d_amd.display.light_level, without grain) through a PeakTracker; this
+    synchronises once per picture. Either value is clamped to [dst_peak, 10000] and goes to the
+    call in a copy of `tonemap`. The other settings are decode_ivf's."""
     from .display import FORMATS, OUT_SEMIPLANAR, DisplayImage, display_picture
     fmt = FORMATS[format] if isinstance(format, str) else int(format)
+    _check_peak(peak, tonemap)
+    tracker = PeakTracker(tonemap.dst_peak) if peak == "measured" else None
     for ev, src in shown_pictures(ctx, data, stream, threads=threads, inloop_filters=inloop_filters,
                                   operating_point=operating_point, all_layers=all_layers,
                                   decode_frame_type=decode_frame_type, frame_size_limit=frame_size_limit):
         color = _shown_colour(ev, src, matrix, tonemap, primaries, transfer, rgb=fmt != OUT_SEMIPLANAR)
         image = DisplayImage(src.w, src.h, src.bpc, src.layout, fmt,
                              out_bpc=tonemap.dst_bpc if tonemap is not None else None)
-        display_picture(ctx, src, image, color, _grain(ev, apply_grain), stream, tonemap)
+        tm = _picture_tonemap(ctx, ev, src, color, tonemap, peak, tracker, stream)
+        display_picture(ctx, src, image, color, _grain(ev, apply_grain), stream, tm)
         yield image, color
 
 
@@ -175,7 +253,7 @@ def fit_crop(w, h, W, H, fit):
 def decode_to_batches(ctx, data, size, batch=8, dtype=None, channels_last=False, mean=None, std=None, fit="stretch",
                       every=1, apply_grain=True, matrix=None, stream=None, inloop_filters=14, threads=1,
                       operating_point=0, all_layers=True, decode_frame_type="all", frame_size_limit=0,
-                      tonemap=None, primaries=None, transfer=None, resample=None):
+                      tonemap=None, primaries=None, transfer=None, resample=None, peak=None):
     """Decode a stream on the device and yield (tensor, [MiColorInfo, ...]) batches for an ML
     consumer: the tensor is (n, 3, H, W) with size = (W, H), n = batch except for a shorter last
     one, of `dtype` (torch.float16 by default; bfloat16, float32 or uint8), contiguous or, with
@@ -187,7 +265,8 @@ def decode_to_batches(ctx, data, size, batch=8, dtype=None, channels_last=False,
     used for each slot; matrix, tonemap, primaries and transfer follow decode_to_tensors's rules
     (with tonemap the slot is mi_display_tensor_tm's: the tone-mapped picture, resized). resample: a
     MiResample (rav1d_amd.display.Resample, "catmull_rom" for models trained on bicubic-resized
-    inputs): the filter of the resize, None the triangle. Each tensor is a fresh allocation
+    inputs): the filter of the resize, None the triangle. peak: decode_to_tensors's, per picture that
+    is output (a skipped picture is not measured). Each tensor is a fresh allocation
     the caller owns, filled by work enqueued on `stream` (synchronise it, or stay on it, before
     reading). The other settings are decode_ivf's."""
     import torch
@@ -198,6 +277,8 @@ def decode_to_batches(ctx, data, size, batch=8, dtype=None, channels_last=False,
         raise ValueError("batch and every must be at least 1")
     fit_crop(1, 1, W, H, fit)      # (an unknown fit fails before any decoding)
     dtype = torch.float16 if dtype is None else dtype
+    _check_peak(peak, tonemap)
+    tracker = PeakTracker(tonemap.dst_peak) if peak == "measured" else None
     tensor, colors = None, []
     shown = enumerate(shown_pictures(ctx, data, stream, threads=threads, inloop_filters=inloop_filters,
                                      operating_point=operating_point, all_layers=all_layers,
@@ -209,8 +290,9 @@ def decode_to_batches(ctx, data, size, batch=8, dtype=None, channels_last=False,
         if tensor is None:
             fmt = torch.channels_last if channels_last else torch.contiguous_format
             tensor, colors = torch.empty((batch, 3, H, W), dtype=dtype, device="cuda", memory_format=fmt), []
+        tm = _picture_tonemap(ctx, ev, src, color, tonemap, peak, tracker, stream)
         display_tensor(ctx, src, tensor[len(colors)], color, _grain(ev, apply_grain),
-                       fit_crop(src.w, src.h, W, H, fit), mean, std, stream, tonemap=tonemap, resample=resample)
+                       fit_crop(src.w, src.h, W, H, fit), mean, std, stream, tonemap=tm, resample=resample)
         colors.append(color)
         if len(colors) == batch:
             yield tensor, colors
@@ -221,7 +303,7 @@ def decode_to_batches(ctx, data, size, batch=8, dtype=None, channels_last=False,
 
 def decode_to_ladder(ctx, data, sizes, bpc=None, fit="stretch", apply_grain=True, stream=None, inloop_filters=14,
                      threads=1, operating_point=0, all_layers=True, decode_frame_type="all", frame_size_limit=0,
-                     resample=None, tonemap=None, target=None, primaries=None, transfer=None, matrix=None):
+                     resample=None, tonemap=None, target=None, primaries=None, transfer=None, matrix=None, peak=None):
     """Decode a stream on the device and yield, per shown picture in output order, (event, rungs):
     the decoder event that showed it and a list with one (Y, UV) pair of device tensors per entry
     of `sizes` ((W, H) luma sizes), the picture as semi-planar YUV at the stream's own subsampling
@@ -239,7 +321,8 @@ def decode_to_ladder(ctx, data, sizes, bpc=None, fit="stretch", apply_grain=True
     overrides of decode_to_tensors, by its rules: with tonemap, a stream that leaves primaries or
     transfer unspecified and has no override raises ValueError before any device work of the
     picture. Without tonemap the overrides are not read and nothing changes (a target on its own is a
-    ValueError: there is no matrix or range conversion without a tone map). Every tensor is
+    ValueError: there is no matrix or range conversion without a tone map). peak: decode_to_tensors's:
+    where a PQ source's src_peak comes from, per shown picture. Every tensor is
     a fresh allocation the caller owns, filled by work enqueued on `stream` (synchronise it, or
     stay on it, before reading). The other settings are decode_ivf's."""
     from .display import ScaledImage, display_scaled, even_crop
@@ -248,6 +331,8 @@ def decode_to_ladder(ctx, data, sizes, bpc=None, fit="stretch", apply_grain=True
         raise ValueError("1 to 8 sizes")
     for W, H in sizes:
         fit_crop(1, 1, W, H, fit)      # (an unknown fit fails before any decoding)
+    _check_peak(peak, tonemap)
+    tracker = PeakTracker(tonemap.dst_peak) if peak == "measured" else None
     for ev, src in shown_pictures(ctx, data, stream, threads=threads, inloop_filters=inloop_filters,
                                   operating_point=operating_point, all_layers=all_layers,
                                   decode_frame_type=decode_frame_type, frame_size_limit=frame_size_limit):
@@ -258,7 +343,8 @@ def decode_to_ladder(ctx, data, sizes, bpc=None, fit="stretch", apply_grain=True
         images = [ScaledImage(W, H, depth if bpc is None else bpc, src.layout,
                               even_crop(fit_crop(src.w, src.h, W, H, fit), src.w, src.h, src.layout))
                   for W, H in sizes]
-        display_scaled(ctx, src, images, color, _grain(ev, apply_grain), stream, resample=resample, tonemap=tonemap,
+        tm = _picture_tonemap(ctx, ev, src, color, tonemap, peak, tracker, stream)
+        display_scaled(ctx, src, images, color, _grain(ev, apply_grain), stream, resample=resample, tonemap=tm,
                        target=target)
         yield ev, [im.tensors() for im in images]
 
