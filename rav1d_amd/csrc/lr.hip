@@ -31,12 +31,32 @@ __constant__ uint16_t k_sgr_params[16][2] = {
     { 0, 1177 },   { 0, 925 },    { 56, 0 },    { 22, 0 },
 };
 
-__device__ __forceinline__ unsigned sgr_x_by_x(unsigned z) {
+constexpr unsigned sgr_x_by_x(unsigned z) {
     // round(256 / (z + 1)), pinned to 255 at z = 0 and 0 at z = 255 (dav1d_sgr_x_by_x)
-    if (z == 0) return 255;
-    if (z >= 255) return 0;
-    return (256 + ((z + 1) >> 1)) / (z + 1);
+    return z == 0 ? 255u : z >= 255 ? 0u : (256 + ((z + 1) >> 1)) / (z + 1);
 }
+// the table as 64 words, built by the compiler: a workgroup copies it to LDS with one load and
+// one store per lane of its first wave
+struct SgrXbyX {
+    uint32_t w[64];
+    constexpr SgrXbyX() : w() {
+        for (unsigned i = 0; i < 64; i++)
+            w[i] = sgr_x_by_x(4 * i) | sgr_x_by_x(4 * i + 1) << 8 | sgr_x_by_x(4 * i + 2) << 16 | sgr_x_by_x(4 * i + 3) << 24;
+    }
+};
+__constant__ SgrXbyX k_sgr_xbyx = SgrXbyX();
+
+// v_dot2c_i32_i16 / v_dot2_u32_u16 on a sample pair as it lies in LDS:
+// a.lo * b.lo + a.hi * b.hi + acc, unclamped, so exact 32-bit integer arithmetic
+typedef short lr_s16x2 __attribute__((ext_vector_type(2)));
+typedef unsigned short lr_u16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ int lr_sd2(uint32_t a, uint32_t b, int acc) {
+    return __builtin_amdgcn_sdot2(__builtin_bit_cast(lr_s16x2, a), __builtin_bit_cast(lr_s16x2, b), acc, false);
+}
+__device__ __forceinline__ unsigned lr_ud2(uint32_t a, uint32_t b, unsigned acc) {
+    return __builtin_amdgcn_udot2(__builtin_bit_cast(lr_u16x2, a), __builtin_bit_cast(lr_u16x2, b), acc, false);
+}
+__device__ __forceinline__ uint32_t pk2(int lo, int hi) { return (uint32_t)(lo & 0xffff) | ((uint32_t)hi << 16); }
 
 template <typename Px>
 __device__ __forceinline__ int ld_px(const uint8_t *base, int64_t stride, int y, int x) {
@@ -58,54 +78,82 @@ __device__ void sgr_ab(const int16_t *win, int *A, int16_t *B, int sh, int tw, u
     if (g >= G || x > tw) return;
     const int nrows = sh + 2;
     // R = 2 keeps A/B on odd rows only: an even row count per group starts every group on an
-    // odd row, so the row parity test below is the same for all lanes (no divergent halves)
+    // odd row, so every lane emits on the same steps of the walk (no divergent halves)
     const int per = R == 2 ? (((nrows + G - 1) / G) + 1) & ~1 : (nrows + G - 1) / G;
     const int y0 = -1 + g * per, y1 = min(-1 + (g + 1) * per, sh + 1);
     if (y0 >= y1) return;
     const uint32_t *col = reinterpret_cast<const uint32_t *>(win + x - 2 + kWX);
     constexpr int W2 = kLrWin / 2;
-    auto hsum = [&](int yy, int &s0, int &q0, int &s1, int &q1) {
+    // One window row's horizontal box sums for both columns, {sum, squares} x {x, x + 1}, on
+    // the sample pairs as they lie in LDS: v_dot2_u32_u16 of a word with itself is the pair's
+    // squares, with (1, 1) its sum. Samples are <= 4095, so every sum is exact in u32.
+    constexpr uint32_t k11 = 0x00010001u;
+    struct Rs { unsigned s0, q0, s1, q1; };
+    auto hsum = [&](int yy) {
         const uint32_t *r = col + (yy + 3) * W2;
         const uint32_t w0 = r[0], w1 = r[1], w2 = r[2];
-        const int v0 = w0 & 0xffff, v1 = w0 >> 16, v2 = w1 & 0xffff, v3 = w1 >> 16, v4 = w2 & 0xffff, v5 = w2 >> 16;
+        Rs o;
         if (R == 2) {
-            const int m = v1 + v2 + v3 + v4, mq = v1 * v1 + v2 * v2 + v3 * v3 + v4 * v4;
-            s0 = m + v0; q0 = mq + v0 * v0; s1 = m + v5; q1 = mq + v5 * v5;
+            // all six, then minus the sample the column does not cover
+            const unsigned sa = lr_ud2(w0, k11, lr_ud2(w1, k11, lr_ud2(w2, k11, 0u)));
+            const unsigned qa = lr_ud2(w0, w0, lr_ud2(w1, w1, lr_ud2(w2, w2, 0u)));
+            const unsigned v0 = w0 & 0xffffu, v5 = w2 >> 16;
+            o.s0 = sa - v5; o.q0 = qa - __umul24(v5, v5); o.s1 = sa - v0; o.q1 = qa - __umul24(v0, v0);
         } else {
-            const int m = v2 + v3, mq = v2 * v2 + v3 * v3;
-            s0 = m + v1; q0 = mq + v1 * v1; s1 = m + v4; q1 = mq + v4 * v4;
+            const unsigned m = lr_ud2(w1, k11, 0u), mq = lr_ud2(w1, w1, 0u);
+            const unsigned v1 = w0 >> 16, v4 = w2 & 0xffffu;
+            o.s0 = m + v1; o.q0 = mq + __umul24(v1, v1); o.s1 = m + v4; o.q1 = mq + __umul24(v4, v4);
         }
+        return o;
     };
-    int rs0[2 * R + 1], rq0[2 * R + 1], rs1[2 * R + 1], rq1[2 * R + 1];
-#pragma unroll
-    for (int k = 0; k < 2 * R; k++) hsum(y0 - R + k, rs0[k], rq0[k], rs1[k], rq1[k]);
+    auto add = [](const Rs &a, const Rs &b) { return Rs{ a.s0 + b.s0, a.q0 + b.q0, a.s1 + b.s1, a.q1 + b.q1 }; };
     const bool c0 = x >= -1, c1 = x + 1 <= tw;
-    for (int y = y0; y < y1; y++) {
-        hsum(y + R, rs0[2 * R], rq0[2 * R], rs1[2 * R], rq1[2 * R]);
-        if (R == 1 || !((y + 1) & 1)) {
-            int sum0 = 0, sq0 = 0, sum1 = 0, sq1 = 0;
+    auto emit = [&](int y, const Rs &t) {
+        const unsigned sums[2] = { t.s0, t.s1 }, sqs[2] = { t.q0, t.q1 };
+        const bool on[2] = { c0, c1 };
 #pragma unroll
-            for (int k = 0; k <= 2 * R; k++) { sum0 += rs0[k]; sq0 += rq0[k]; sum1 += rs1[k]; sq1 += rq1[k]; }
-            const int sums[2] = { sum0, sum1 }, sqs[2] = { sq0, sq1 };
-            const bool on[2] = { c0, c1 };
-#pragma unroll
-            for (int e = 0; e < 2; e++) {
-                // a, b < 2^21 (25 squares of 8-bit-scaled samples) and xv * one_by_x < 2^17, sums
-                // < 2^17: 24-bit multiplies (full rate) except p * s, which wraps in u32 as the
-                // reference's does
-                const int a = (sqs[e] + ((1 << (2 * bdm8)) >> 1)) >> (2 * bdm8);
-                const int b = (sums[e] + ((1 << bdm8) >> 1)) >> bdm8;
-                const unsigned p = (unsigned)max((int)__umul24((unsigned)a, (unsigned)n) - (int)__umul24((unsigned)b, (unsigned)b), 0);
-                const unsigned z = (p * s + (1u << 19)) >> 20;
-                const unsigned xv = xbyx[min(z, 255u)];
-                if (on[e]) {
-                    A[(y + 1) * kLrAB + x + e + 1] = (int)((__umul24(__umul24(xv, one_by_x), (unsigned)sums[e]) + (1u << 11)) >> 12);
-                    B[(y + 1) * kLrAB + x + e + 1] = (int16_t)xv;
-                }
+        for (int e = 0; e < 2; e++) {
+            // a, b < 2^21 (25 squares of 8-bit-scaled samples) and xv * one_by_x < 2^17, sums
+            // < 2^17: 24-bit multiplies (full rate) except p * s, which wraps in u32 as the
+            // reference's does
+            const int a = (int)((sqs[e] + ((1u << (2 * bdm8)) >> 1)) >> (2 * bdm8));
+            const int b = (int)((sums[e] + ((1u << bdm8) >> 1)) >> bdm8);
+            const unsigned p = (unsigned)max((int)__umul24((unsigned)a, (unsigned)n) - (int)__umul24((unsigned)b, (unsigned)b), 0);
+            const unsigned z = (p * s + (1u << 19)) >> 20;
+            const unsigned xv = xbyx[min(z, 255u)];
+            if (on[e]) {
+                A[(y + 1) * kLrAB + x + e + 1] = (int)((__umul24(__umul24(xv, one_by_x), sums[e]) + (1u << 11)) >> 12);
+                B[(y + 1) * kLrAB + x + e + 1] = (int16_t)xv;
             }
         }
-#pragma unroll
-        for (int k = 0; k < 2 * R; k++) { rs0[k] = rs0[k + 1]; rq0[k] = rq0[k + 1]; rs1[k] = rs1[k + 1]; rq1[k] = rq1[k + 1]; }
+    };
+    // The walk keeps no ring of rows to shift. Two slots swap roles every step, so the loop is
+    // unrolled over that period of two steps and every slot is a fixed register.
+    if (R == 2) {
+        // a step is an emitting row y and the row after it: the five rows y-2 .. y+2 are the
+        // two row pairs before y + 2, kept as sums, and that row
+        Rs pa = add(hsum(y0 - 2), hsum(y0 - 1)), pb = add(hsum(y0), hsum(y0 + 1));
+        for (int y = y0; y < y1; y += 4) {
+            Rs t = add(pa, pb), nx = hsum(y + 2);
+            emit(y, add(t, nx));
+            if (y + 2 >= y1) break;
+            pa = add(nx, hsum(y + 3));
+            t = add(pb, pa); nx = hsum(y + 4);
+            emit(y + 2, add(t, nx));
+            if (y + 4 >= y1) break;
+            pb = add(nx, hsum(y + 5));
+        }
+    } else {
+        Rs ra = hsum(y0 - 1), rb = hsum(y0);
+        for (int y = y0; y < y1; y += 2) {
+            Rs t = add(ra, rb);
+            ra = hsum(y + 1);
+            emit(y, add(t, ra));
+            if (y + 1 >= y1) break;
+            t = add(rb, ra);
+            rb = hsum(y + 2);
+            emit(y + 1, add(t, rb));
+        }
     }
 }
 
@@ -163,28 +211,40 @@ __device__ __forceinline__ void sgr_px(const int *A, const int16_t *B, int r0, i
     }
 }
 
-// Wiener horizontal pass (looprestoration.rs:299-335) by column pairs: lane (rg, cp) filters
-// columns 2cp and 2cp + 1 of rows rg, rg + 16, ...: the ten samples x-4 .. x+5 are five aligned
-// 32-bit LDS reads (2.5 per output instead of 7) and the pair is one 32-bit store.
+// Wiener horizontal pass (looprestoration.rs:299-335) by column pairs and row pairs: lane
+// (rg, cp) filters columns 2cp and 2cp + 1 of rows 2rg, 2rg + 1, then 32 rows on, ... The ten
+// samples x-4 .. x+5 are five aligned 32-bit LDS reads, and each output is four v_dot2 on the
+// words as they lie: column x against the tap pairs (0,f0) (f1,f2) (f3,f4) (f5,f6) from word
+// (x-4,x-3) on, column x + 1 against (f0,f1) (f2,f3) (f4,f5) (f6,0) from word (x-2,x-1) on.
+// The output is stored for the vertical pass's dot products: hor[rp][x] is the 32-bit word
+// (h[2rp][x], h[2rp + 1][x]), one 64-bit store per lane and row pair. Row wr of an odd wr is
+// stored as zero (it only ever meets a zero tap); the window row read for it is not staged but
+// lies inside the 70-row window, since an odd wr is at most 69.
 __device__ __forceinline__ void wiener_hor(const int16_t *win, int16_t *hor, int wr, int tw, const int (&fh)[7],
                                            int bd, int rbh, int clip_h) {
     const int cp = threadIdx.x & 31, rg = threadIdx.x >> 5, x = 2 * cp;
     if (x >= tw) return;
-    for (int rr = rg; rr < wr; rr += kNT / 32) {
-        const uint32_t *w = reinterpret_cast<const uint32_t *>(win + rr * kLrWin + x + kWX - 4);
-        int v[10];
+    const uint32_t te[4] = { pk2(0, fh[0]), pk2(fh[1], fh[2]), pk2(fh[3], fh[4]), pk2(fh[5], fh[6]) };
+    const uint32_t to[4] = { pk2(fh[0], fh[1]), pk2(fh[2], fh[3]), pk2(fh[4], fh[5]), pk2(fh[6], 0) };
+    const int rnd = (1 << (bd + 6)) + (1 << (rbh - 1));
+    for (int rp = rg; 2 * rp < wr; rp += kNT / 32) {
+        uint32_t o[2][2];
 #pragma unroll
-        for (int k = 0; k < 5; k++) {
-            const uint32_t q = w[k];
-            v[2 * k] = (int)(int16_t)(q & 0xffffu);
-            v[2 * k + 1] = (int)(int16_t)(q >> 16);
+        for (int h = 0; h < 2; h++) {
+            const int rr = 2 * rp + h;
+            const uint32_t *w = reinterpret_cast<const uint32_t *>(win + rr * kLrWin + x + kWX - 4);
+            uint32_t q[5];
+#pragma unroll
+            for (int k = 0; k < 5; k++) q[k] = w[k];
+            int s0 = rnd, s1 = rnd;
+#pragma unroll
+            for (int k = 0; k < 4; k++) { s0 = lr_sd2(q[k], te[k], s0); s1 = lr_sd2(q[k + 1], to[k], s1); }
+            const bool in = rr < wr;
+            o[0][h] = in ? (uint32_t)min(max(s0 >> rbh, 0), clip_h) : 0u;
+            o[1][h] = in ? (uint32_t)min(max(s1 >> rbh, 0), clip_h) : 0u;
         }
-        int s0 = 1 << (bd + 6), s1 = s0;
-#pragma unroll
-        for (int t = 0; t < 7; t++) { s0 += v[t + 1] * fh[t]; s1 += v[t + 2] * fh[t]; }
-        const int h0 = min(max((s0 + (1 << (rbh - 1))) >> rbh, 0), clip_h);
-        const int h1 = min(max((s1 + (1 << (rbh - 1))) >> rbh, 0), clip_h);
-        *reinterpret_cast<uint32_t *>(hor + rr * 64 + x) = (uint32_t)(h0 & 0xffff) | ((uint32_t)h1 << 16);
+        *reinterpret_cast<uint2 *>(reinterpret_cast<uint32_t *>(hor) + rp * 64 + x) =
+            make_uint2(o[0][0] | (o[0][1] << 16), o[1][0] | (o[1][1] << 16));
     }
 }
 
@@ -295,36 +355,42 @@ __device__ __forceinline__ void sgr_pairs(int *A, int16_t *B, const int16_t *win
 }
 
 // Wiener vertical pass (looprestoration.rs:337-370) by column pairs: lane (rg, cp) filters
-// columns 2cp, 2cp + 1 of rows 4rg .. 4rg + 3 from ten 32-bit reads of the horizontal output
-// (one per row, both columns) and stores each output pair as one 32-bit word.
-__device__ __forceinline__ void wiener_ver(const int16_t *hor, int16_t *B, int wr, int sh, int tw, const int (&fv)[7],
+// columns 2cp, 2cp + 1 of rows 4rg .. 4rg + 3 from five 64-bit reads of the horizontal output,
+// the row pairs (4rg + 2j, 4rg + 2j + 1) of both columns. The horizontal output is at most
+// 32767, a signed 16-bit operand, so an output is four v_dot2: an even row against the tap
+// pairs (f0,f1) (f2,f3) (f4,f5) (f6,0) from its own pair on, an odd row against (0,f0) (f1,f2)
+// (f3,f4) (f5,f6). Pairs past row wr feed only rows past sh, which are not produced.
+__device__ __forceinline__ void wiener_ver(const int16_t *hor, int16_t *B, int sh, int tw, const int (&fv)[7],
                                            int bd, int rbv, int bdmax) {
     const int cp = threadIdx.x & 31, rg = threadIdx.x >> 5, x = 2 * cp;
     const int r0 = rg * 4, r1 = min(r0 + 4, sh);
     if (x >= tw || r0 >= r1) return;
-    const int off = 1 << (bd + rbv - 1);
-    int h0[10], h1[10];
+    // the unguarded reads below end at row pair 2 (kNT / 32 - 1) + 4 of the 35 that hor holds
+    static_assert(2 * (kNT / 32 - 1) + 4 < 35 && 35 * 64 <= 66 * kLrAB, "wiener_ver reads past hor");
+    const uint32_t te[4] = { pk2(fv[0], fv[1]), pk2(fv[2], fv[3]), pk2(fv[4], fv[5]), pk2(fv[6], 0) };
+    const uint32_t to[4] = { pk2(0, fv[0]), pk2(fv[1], fv[2]), pk2(fv[3], fv[4]), pk2(fv[5], fv[6]) };
+    const int rnd = (1 << (rbv - 1)) - (1 << (bd + rbv - 1));
+    uint2 hp[5];
 #pragma unroll
-    for (int q = 0; q < 10; q++) {
-        const uint32_t w = r0 + q < wr ? *reinterpret_cast<const uint32_t *>(hor + (r0 + q) * 64 + x) : 0u;
-        h0[q] = (int)(w & 0xffffu);
-        h1[q] = (int)(w >> 16);
-    }
+    for (int j = 0; j < 5; j++) hp[j] = *reinterpret_cast<const uint2 *>(reinterpret_cast<const uint32_t *>(hor) + (2 * rg + j) * 64 + x);
 #pragma unroll
     for (int q = 0; q < 4; q++) {
         if (r0 + q < r1) {
-            int s0 = -off, s1 = -off;
+            int s0 = rnd, s1 = rnd;
 #pragma unroll
-            for (int t = 0; t < 7; t++) { s0 += h0[q + t] * fv[t]; s1 += h1[q + t] * fv[t]; }
-            const int o0 = min(max((s0 + (1 << (rbv - 1))) >> rbv, 0), bdmax);
-            const int o1 = min(max((s1 + (1 << (rbv - 1))) >> rbv, 0), bdmax);
+            for (int k = 0; k < 4; k++) {
+                const uint32_t t = q & 1 ? to[k] : te[k];
+                s0 = lr_sd2(hp[(q >> 1) + k].x, t, s0);
+                s1 = lr_sd2(hp[(q >> 1) + k].y, t, s1);
+            }
+            const int o0 = min(max(s0 >> rbv, 0), bdmax);
+            const int o1 = min(max(s1 >> rbv, 0), bdmax);
             *reinterpret_cast<uint32_t *>(B + (r0 + q) * 64 + x) = (uint32_t)(o0 & 0xffff) | ((uint32_t)o1 << 16);
         }
     }
 }
 
 // 8 pixels as int16 pairs in a uint4 (u16: one 16-B load; u8: one 8-B load widened)
-__device__ __forceinline__ uint32_t pk2(int lo, int hi) { return (uint32_t)(lo & 0xffff) | ((uint32_t)hi << 16); }
 template <typename Px>
 __device__ __forceinline__ uint4 load8(const Px *p) {
     if constexpr (sizeof(Px) == 2) {
@@ -378,17 +444,13 @@ __device__ __forceinline__ void lr_wiener_tile(const int (&fh)[7], const int (&f
         const int clip_h = (1 << (bd + 1 + 7 - rbh)) - 1;
         wiener_hor(win, hor, wr, tw, fh, bd, rbh, clip_h);
         __syncthreads();
-        wiener_ver(hor, B, wr, sh, tw, fv, bd, rbv, bdmax);
+        wiener_ver(hor, B, sh, tw, fv, bd, rbv, bdmax);
         __syncthreads();
     }
 }
 __device__ __forceinline__ void lr_sgr_tile(int s0, int s1, int w0, int w1, int16_t *win, int *A, int16_t *B, int sh,
-                                            int tw, int bd, uint8_t *xbyx /* LDS [256] */) {
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-    const int r0 = ty * kNR, r1 = min(r0 + kNR, sh);
+                                            int tw, int bd, const uint8_t *xbyx /* LDS [256], staged with win */) {
     const int bdmax = (1 << bd) - 1;
-    if (threadIdx.x < 256) xbyx[threadIdx.x] = (uint8_t)sgr_x_by_x(threadIdx.x);
-    __syncthreads();
     const int bdm8 = bd - 8;
     sgr_pairs(A, B, win, sh, tw, bdm8, s0, s1, w0, w1, xbyx, bdmax);
     __syncthreads();
@@ -400,7 +462,7 @@ __global__ __launch_bounds__(kNT) __attribute__((amdgpu_waves_per_eu(8))) void l
     __shared__ __attribute__((aligned(16))) int16_t win[70 * kLrWin];
     __shared__ __attribute__((aligned(16))) int A[66 * kLrAB];
     __shared__ __attribute__((aligned(16))) int16_t B[66 * kLrAB];
-    int16_t *hor = reinterpret_cast<int16_t *>(A);    // Wiener: [70][64] aliases A
+    int16_t *hor = reinterpret_cast<int16_t *>(A);    // Wiener: 35 row pairs x 64 words, aliases A
 
     KTL(0);
     const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
@@ -467,6 +529,11 @@ __global__ __launch_bounds__(kNT) __attribute__((amdgpu_waves_per_eu(8))) void l
     const int wr = sh + 6;
     constexpr int kNV = kLrWin / 8;                   // vectors per window row
     constexpr int kSV = (70 * kNV + kNT - 1) / kNT;   // vectors per lane
+    // (self-guided units: the x_by_x table rides along, one word per lane of the first wave)
+    __shared__ __attribute__((aligned(16))) uint8_t xbyx[256];
+    const bool xb = type >= 3 && threadIdx.x < 64;
+    uint32_t xw = 0;
+    if (xb) xw = k_sgr_xbyx.w[threadIdx.x];
     uint4 sv[kSV];
 #pragma unroll
     for (int q = 0; q < kSV; q++) {
@@ -495,6 +562,7 @@ __global__ __launch_bounds__(kNT) __attribute__((amdgpu_waves_per_eu(8))) void l
         const int rr = i / kNV;
         if (rr < wr) *reinterpret_cast<uint4 *>(&win[rr * kLrWin + 8 * (i % kNV)]) = sv[q];
     }
+    if (xb) reinterpret_cast<uint32_t *>(xbyx)[threadIdx.x] = xw;
     __syncthreads();
     KTL(1);
 
@@ -515,7 +583,7 @@ __global__ __launch_bounds__(kNT) __attribute__((amdgpu_waves_per_eu(8))) void l
         wiener_hor(win, hor, wr, tw, fh, bd, rbh, clip_h);
         __syncthreads();
         KTL(2);
-        wiener_ver(hor, B, wr, sh, tw, fv, bd, rbv, bdmax);
+        wiener_ver(hor, B, sh, tw, fv, bd, rbv, bdmax);
         __syncthreads();
         KTL(3);
         store_tile<Px>(B, O, st, S, sh, x0, tw);
@@ -524,9 +592,6 @@ __global__ __launch_bounds__(kNT) __attribute__((amdgpu_waves_per_eu(8))) void l
     }
 
     // ---- self-guided (looprestoration.rs:566-912) ----
-    __shared__ uint8_t xbyx[256];
-    if (threadIdx.x < 256) xbyx[threadIdx.x] = (uint8_t)sgr_x_by_x(threadIdx.x);
-    __syncthreads();
     const int sidx = type - 3;
     const int s0 = k_sgr_params[sidx][0], s1 = k_sgr_params[sidx][1];
     const int w0 = u->sgr_weights[0];
@@ -548,7 +613,7 @@ __global__ __launch_bounds__(kNT) void lr_call_kernel(LrCallArgs a) {
     __shared__ __attribute__((aligned(16))) int16_t win[70 * kLrWin];
     __shared__ __attribute__((aligned(16))) int A[66 * kLrAB];
     __shared__ __attribute__((aligned(16))) int16_t B[66 * kLrAB];
-    int16_t *hor = reinterpret_cast<int16_t *>(A);
+    int16_t *hor = reinterpret_cast<int16_t *>(A);    // Wiener: 35 row pairs x 64 words, aliases A
     const int x0 = blockIdx.x * 64, tw = min(64, a.w - x0), h = a.h;
     const bool hl = a.edges & 1, hr = a.edges & 2, ht = a.edges & 4, hb = a.edges & 8;
     const Px *p = reinterpret_cast<const Px *>(a.p), *lpf = reinterpret_cast<const Px *>(a.lpf);
@@ -570,10 +635,11 @@ __global__ __launch_bounds__(kNT) void lr_call_kernel(LrCallArgs a) {
         }
         win[i] = (int16_t)v;
     }
+    __shared__ __attribute__((aligned(16))) uint8_t xbyx[256];
+    if (!a.tp.wiener && threadIdx.x < 64) reinterpret_cast<uint32_t *>(xbyx)[threadIdx.x] = k_sgr_xbyx.w[threadIdx.x];
     __syncthreads();
     if (a.tp.wiener) lr_wiener_tile(a.tp.fh, a.tp.fv, win, B, hor, h, tw, a.bd);
     else {
-        __shared__ uint8_t xbyx[256];
         lr_sgr_tile(a.tp.s0, a.tp.s1, a.tp.w0, a.tp.w1, win, A, B, h, tw, a.bd, xbyx);
     }
     // output tile -> the packed w x h result
