@@ -1,8 +1,8 @@
 /*
- * oracle/census.h — event counters and single-decision mutants for the in-loop filter
- * restatements (TEST INFRASTRUCTURE ONLY).
+ * oracle/census.h — event counters and single-decision mutants for the in-loop filter and
+ * inverse-transform restatements (TEST INFRASTRUCTURE ONLY).
  *
- * loopfilter.c, cdef.c and lr.c are compiled twice from the same sources. The plain build
+ * loopfilter.c, cdef.c, lr.c and itx.c are compiled twice from the same sources. The plain build
  * (liboracle.so) sees every macro below expand to nothing or to the constant 0, so it holds
  * no counter, no extra branch and no global. The census build (liboracle_census.so,
  * -DORACLE_CENSUS) counts how often each decision of the filters is taken and how often it
@@ -32,7 +32,14 @@ enum {
     MUT_WIENER_NO_HCLIP_HI = 28,       /* horizontal pass: upper clip bound removed */
     MUT_SGR_PS_I32 = 29,               /* p * s taken as int32 before its shift */
     MUT_SGR_XSUM_I32 = 30,             /* x * sum * one_by_x taken as int32 before its shift */
-    MUT_COUNT = 31
+    /* inverse transforms (itx.c) */
+    MUT_ITX_ROT_I32 = 31,              /* rotations, S12 and H181 evaluated in wrapping 32-bit */
+    MUT_ITX_NO_CLIP = 32,              /* the 1-D intermediate CL() removed */
+    MUT_ITX_NO_MIDCLIP = 33,           /* the clip between the row and the column pass removed */
+    MUT_ITX_MID_I16 = 34,              /* the row-to-column hand-off truncated to int16 */
+    MUT_ITX_RES_I16 = 35,              /* the residual (c + 8) >> 4 truncated to int16 */
+    MUT_ITX_WHT_MID_I16 = 36,          /* the WHT row result truncated to int16 */
+    MUT_COUNT = 37
 };
 
 /* ---- deblock comparisons, in the order the reference evaluates them ---- */
@@ -86,7 +93,20 @@ enum {
     CEN_SGR_OUT_LO = CEN_SGR_XSUM31 + 2, CEN_SGR_OUT_HI,
     CEN_LR_SET,                                     /* [3 planes][16 sets] unit-stripes restored */
     CEN_LR_WIENER = CEN_LR_SET + 48,                /* [3 planes] */
-    CEN_COUNT = CEN_LR_WIENER + 3
+    /* inverse transforms: every group is [3], indexed by bit depth (8, 10, 12) */
+    CEN_ITX_ROW_CLIP_LO = CEN_LR_WIENER + 3,        /* 1-D intermediate clip, row pass */
+    CEN_ITX_ROW_CLIP_HI = CEN_ITX_ROW_CLIP_LO + 3,
+    CEN_ITX_COL_CLIP_LO = CEN_ITX_ROW_CLIP_HI + 3,  /* ... column pass */
+    CEN_ITX_COL_CLIP_HI = CEN_ITX_COL_CLIP_LO + 3,
+    CEN_ITX_MID_CLIP_LO = CEN_ITX_COL_CLIP_HI + 3,  /* hand-off clip between the passes */
+    CEN_ITX_MID_CLIP_HI = CEN_ITX_MID_CLIP_LO + 3,
+    CEN_ITX_PX_CLIP_0 = CEN_ITX_MID_CLIP_HI + 3,    /* pixel clip at 0 / bdmax */
+    CEN_ITX_PX_CLIP_MAX = CEN_ITX_PX_CLIP_0 + 3,
+    CEN_ITX_RES_GT_I16 = CEN_ITX_PX_CLIP_MAX + 3,   /* residual (c + 8) >> 4 beyond int16 */
+    CEN_ITX_WHT_MID_GT_I16 = CEN_ITX_RES_GT_I16 + 3, /* WHT row result beyond int16 */
+    CEN_ITX_ROT_GE_2P31 = CEN_ITX_WHT_MID_GT_I16 + 3, /* exact rotation sum (its +2048 included, ADST4's
+                                                     * four-term sums too) at or beyond 2^31 in magnitude */
+    CEN_COUNT = CEN_ITX_ROT_GE_2P31 + 3
 };
 
 #ifdef ORACLE_CENSUS

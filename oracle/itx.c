@@ -16,22 +16,51 @@
  * This restatement evaluates every rotation in 64-bit, so it computes the same exact
  * values for any input without the rewrite. CLIP points, rounding points and output
  * negations are kept exactly where the reference has them.
+ *
+ * Compiled a second time into liboracle_census.so (-DORACLE_CENSUS, census.h): there the clips
+ * and the sums below count how often they fire, and single-decision mutants can be switched
+ * on. The plain build sees none of that: SUM() is the bare shift and cl1d() the bare clip.
  */
 #include <stdint.h>
 #include <string.h>
 #include "oracle.h"
+#include "census.h"
 
 typedef int64_t i64;
 
+#ifdef ORACLE_CENSUS
+static int itx_bd;     /* bit-depth index (8, 10, 12 -> 0, 1, 2), set by oracle_itxfm_add */
+static int itx_pass;   /* 0: row pass, 1: column pass */
+/* a rounded sum of products before its shift: counted when the exact value is at or beyond
+ * 2^31 in magnitude; the mutant keeps its low 32 bits, as wrapping 32-bit arithmetic would */
+static inline int itx_sum(i64 v, int sh)
+{
+    CEN_IF(v >= ((i64)1 << 31) || v <= -((i64)1 << 31), CEN_ITX_ROT_GE_2P31 + itx_bd);
+    if (MUT(MUT_ITX_ROT_I32)) v = (int32_t)(uint32_t)(uint64_t)v;
+    return (int)(v >> sh);
+}
+#define SUM(v, sh) itx_sum((v), (sh))
+#else
+#define SUM(v, sh) ((int)((v) >> (sh)))
+#endif
+
 /* rounded rotation term: (a*ca + b*cb + 2048) >> 12, exact in 64-bit */
-#define R12(a, ca, b, cb) ((int)(((i64)(a) * (ca) + (i64)(b) * (cb) + 2048) >> 12))
+#define R12(a, ca, b, cb) SUM((i64)(a) * (ca) + (i64)(b) * (cb) + 2048, 12)
 /* single-input scale by c/4096 with rounding */
-#define S12(a, ca) ((int)(((i64)(a) * (ca) + 2048) >> 12))
+#define S12(a, ca) SUM((i64)(a) * (ca) + 2048, 12)
 /* (x * 181 + 128) >> 8 : multiply by 1/sqrt(2) */
-#define H181(x) ((int)(((i64)(x) * 181 + 128) >> 8))
+#define H181(x) SUM((i64)(x) * 181 + 128, 8)
 
 static inline int clipi(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
-#define CL(x) clipi((x), lo, hi)
+/* the 1-D kernels' intermediate clip */
+static inline int cl1d(int v, int lo, int hi)
+{
+    CEN_IF(v < lo, CEN_ITX_ROW_CLIP_LO + 6 * itx_pass + itx_bd);
+    CEN_IF(v > hi, CEN_ITX_ROW_CLIP_HI + 6 * itx_pass + itx_bd);
+    if (MUT(MUT_ITX_NO_CLIP)) return v;
+    return clipi(v, lo, hi);
+}
+#define CL(x) cl1d((x), lo, hi)
 
 /* ---------------- DCT (itx_1d.rs dct4..dct64; itx_1d.c:66-781) ---------------- */
 /* `half` mirrors the reference's tx64 flag: only the first half of the inputs is nonzero. */
@@ -343,10 +372,10 @@ static void dct64(int32_t *c, ptrdiff_t s, int lo, int hi)
 static void adst4(const int32_t *in, ptrdiff_t is, int32_t *out, ptrdiff_t os)
 {
     const i64 x0 = in[0], x1 = in[is], x2 = in[2 * is], x3 = in[3 * is];
-    out[0] = (int)((1321 * x0 + 3803 * x2 + 2482 * x3 + 3344 * x1 + 2048) >> 12);
-    out[os] = (int)((2482 * x0 - 1321 * x2 - 3803 * x3 + 3344 * x1 + 2048) >> 12);
-    out[2 * os] = (int)((209 * (x0 - x2 + x3) + 128) >> 8);
-    out[3 * os] = (int)((3803 * x0 + 2482 * x2 - 1321 * x3 - 3344 * x1 + 2048) >> 12);
+    out[0] = SUM(1321 * x0 + 3803 * x2 + 2482 * x3 + 3344 * x1 + 2048, 12);
+    out[os] = SUM(2482 * x0 - 1321 * x2 - 3803 * x3 + 3344 * x1 + 2048, 12);
+    out[2 * os] = SUM(209 * (x0 - x2 + x3) + 128, 8);
+    out[3 * os] = SUM(3803 * x0 + 2482 * x2 - 1321 * x3 - 3344 * x1 + 2048, 12);
 }
 
 static void adst8(const int32_t *in, ptrdiff_t is, int32_t *out, ptrdiff_t os, int lo, int hi)
@@ -521,7 +550,12 @@ static const uint8_t ty_row[16] = { K_DCT, K_DCT, K_ADST, K_ADST, K_DCT, K_FLIPA
                                     K_FLIPADST, K_ADST, K_IDENTITY, K_IDENTITY, K_DCT, K_IDENTITY,
                                     K_ADST, K_IDENTITY, K_FLIPADST };
 
-static inline int clip_px(int v, int bdmax) { return v < 0 ? 0 : v > bdmax ? bdmax : v; }
+static inline int clip_px(int v, int bdmax)
+{
+    CEN_IF(v < 0, CEN_ITX_PX_CLIP_0 + itx_bd);
+    CEN_IF(v > bdmax, CEN_ITX_PX_CLIP_MAX + itx_bd);
+    return v < 0 ? 0 : v > bdmax ? bdmax : v;
+}
 
 void oracle_itxfm_add(int tx, int txtp, void *dst_, ptrdiff_t stride, void *coeff_,
                       int eob, int bdmax)
@@ -536,6 +570,7 @@ void oracle_itxfm_add(int tx, int txtp, void *dst_, ptrdiff_t stride, void *coef
 #define SETPX(x, y, v) do { if (hbd) dst16[(y) * ps + (x)] = (uint16_t)(v); \
                             else dst8[(y) * ps + (x)] = (uint8_t)(v); } while (0)
 #define CF(i) (hbd ? cf32[i] : (int)cf16[i])
+    CEN_ONLY(itx_bd = bdmax > 1023 ? 2 : hbd; itx_pass = 0;)
 
     if (txtp == 16) {
         /* lossless WHT, itx_tmpl.c:162-181 / itx.rs:475-526 */
@@ -543,6 +578,10 @@ void oracle_itxfm_add(int tx, int txtp, void *dst_, ptrdiff_t stride, void *coef
         for (int y = 0; y < 4; y++) {
             for (int x = 0; x < 4; x++) t[y * 4 + x] = CF(y + x * 4) >> 2;
             wht4(&t[y * 4], 1);
+            for (int x = 0; x < 4; x++) {
+                CEN_IF(t[y * 4 + x] != (int16_t)t[y * 4 + x], CEN_ITX_WHT_MID_GT_I16 + itx_bd);
+                if (MUT(MUT_ITX_WHT_MID_I16)) t[y * 4 + x] = (int16_t)t[y * 4 + x];
+            }
         }
         if (hbd) memset(cf32, 0, 16 * 4); else memset(cf16, 0, 16 * 2);
         for (int x = 0; x < 4; x++) wht4(&t[x], 4);
@@ -587,12 +626,23 @@ void oracle_itxfm_add(int tx, int txtp, void *dst_, ptrdiff_t stride, void *coef
     }
     if (hbd) memset(cf32, 0, sizeof(int32_t) * sw * sh);
     else memset(cf16, 0, sizeof(int16_t) * sw * sh);
-    for (int i = 0; i < w * sh; i++)
-        tmp[i] = clipi((tmp[i] + rnd) >> shift, col_lo, col_hi);
+    for (int i = 0; i < w * sh; i++) {
+        int v = (tmp[i] + rnd) >> shift;
+        CEN_IF(v < col_lo, CEN_ITX_MID_CLIP_LO + itx_bd);
+        CEN_IF(v > col_hi, CEN_ITX_MID_CLIP_HI + itx_bd);
+        if (!MUT(MUT_ITX_NO_MIDCLIP)) v = clipi(v, col_lo, col_hi);
+        if (MUT(MUT_ITX_MID_I16)) v = (int16_t)v;
+        tmp[i] = v;
+    }
+    CEN_ONLY(itx_pass = 1;)
     for (int x = 0; x < w; x++) oracle_itx_1d(ck, h, &tmp[x], w, col_lo, col_hi);
     for (int y = 0; y < h; y++)
-        for (int x = 0; x < w; x++)
-            SETPX(x, y, clip_px(PX(x, y) + ((tmp[y * w + x] + 8) >> 4), bdmax));
+        for (int x = 0; x < w; x++) {
+            int r = (tmp[y * w + x] + 8) >> 4;
+            CEN_IF(r != (int16_t)r, CEN_ITX_RES_GT_I16 + itx_bd);
+            if (MUT(MUT_ITX_RES_I16)) r = (int16_t)r;
+            SETPX(x, y, clip_px(PX(x, y) + r, bdmax));
+        }
 #undef PX
 #undef SETPX
 #undef CF

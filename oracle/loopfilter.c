@@ -63,6 +63,11 @@ int oracle_census_layout(int what)
         CEN_CDEF_PX_OUT0, CEN_CDEF_PX_OUTMAX, CEN_WIENER_HCLIP_LO, CEN_WIENER_HCLIP_HI,
         CEN_WIENER_VCLIP_LO, CEN_WIENER_VCLIP_HI, CEN_SGR_Z0, CEN_SGR_Z255, CEN_SGR_PS31,
         CEN_SGR_XSUM31, CEN_SGR_OUT_LO, CEN_SGR_OUT_HI, CEN_LR_SET, CEN_LR_WIENER,
+        CEN_ITX_ROW_CLIP_LO, CEN_ITX_ROW_CLIP_HI, CEN_ITX_COL_CLIP_LO, CEN_ITX_COL_CLIP_HI,
+        CEN_ITX_MID_CLIP_LO, CEN_ITX_MID_CLIP_HI, CEN_ITX_PX_CLIP_0, CEN_ITX_PX_CLIP_MAX,
+        CEN_ITX_RES_GT_I16, CEN_ITX_WHT_MID_GT_I16, CEN_ITX_ROT_GE_2P31,
+        MUT_ITX_ROT_I32, MUT_ITX_NO_CLIP, MUT_ITX_NO_MIDCLIP, MUT_ITX_MID_I16, MUT_ITX_RES_I16,
+        MUT_ITX_WHT_MID_I16,
     };
     return what >= 0 && what < (int)(sizeof(v) / sizeof(v[0])) ? v[what] : -1;
 }

@@ -853,8 +853,9 @@ __device__ __forceinline__ int itx_rows(const MiTxBlock &b, Cf *cf, bool zero, i
 #pragma unroll
                 for (int x = 0; x < 4; x++) r[x] >>= 2;
                 iwht4(r);
+                // unclipped, 18 bits at 10 bpc: through a 32-bit view of tmp (itx.hip itx_size)
 #pragma unroll
-                for (int x = 0; x < 4; x++) tmp[j * LS + x] = (Lt)r[x];
+                for (int x = 0; x < 4; x++) reinterpret_cast<int *>(tmp)[j * 4 + x] = r[x];
             }
         } else {
             itx1d<Wide, Wd>(row_kind_ip(b.txtp), r, row_lo, row_hi);
@@ -881,6 +882,8 @@ __device__ __forceinline__ void itx_cols(const MiTxBlock &b, int bdmax, int16_t 
         for (int y = 0; y < Ht; y++) c[y] = y < SH ? (int)tmp[y * LS + j] : 0;
         if (TX == 0 && b.txtp == 16) {
             if constexpr (TX == 0) {
+#pragma unroll
+                for (int y = 0; y < 4; y++) c[y] = reinterpret_cast<const int *>(tmp)[y * 4 + j];   // (not the slab read above)
                 iwht4(c);
 #pragma unroll
                 for (int y = 0; y < 4; y++) res[y * Wd + j] = (int16_t)clampi(c[y], -32768, 32767);

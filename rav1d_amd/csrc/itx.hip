@@ -122,6 +122,15 @@ __device__ __forceinline__ void itx_size(const ItxArgs &a, int lwg, Lt *lds) {
     const int pw3[3] = { a.pw[0], a.pw[1], a.pw[2] }, ph3[3] = { a.ph[0], a.ph[1], a.ph[2] };
     const int bdmax = a.bdmax;
     Lt *tmp = lds + lb * SH * LS;
+    // WHT_WHT (lossless 4x4) hands its row result to the column pass unclipped: 18 bits at 10 bpc
+    // (coefficients of 131071 give 65534), which the int16 slab of 8 / 10 bpc cannot hold. Those
+    // blocks use a 32-bit 4x4 of their own behind the workgroup's slabs
+    int *wt = nullptr;
+    if constexpr (TX == 0) {
+        static_assert((BPW * SH * LS * sizeof(Lt)) % 4 == 0, "the 32-bit view is aligned");
+        static_assert(BPW * SH * LS * sizeof(Lt) + BPW * 16 * sizeof(int) <= itx_lds_max(false) * sizeof(Lt), "LDS for it");
+        wt = reinterpret_cast<int *>(lds + BPW * SH * LS) + lb * 16;
+    }
 
     // ---- 1. every round's descriptor, destination chunks and DC coefficient in flight at
     // once: small blocks carry little work per load, so a workgroup takes ROUNDS x BPW of
@@ -230,7 +239,7 @@ __device__ __forceinline__ void itx_size(const ItxArgs &a, int lwg, Lt *lds) {
                 for (int x = 0; x < 4; x++) r[x] >>= 2;
                 iwht4(r);
 #pragma unroll
-                for (int x = 0; x < 4; x++) tmp[j * LS + x] = (Lt)r[x];
+                for (int x = 0; x < 4; x++) wt[j * 4 + x] = r[x];
             }
         }
         if (!wht) {
@@ -251,9 +260,13 @@ __device__ __forceinline__ void itx_size(const ItxArgs &a, int lwg, Lt *lds) {
         for (int y = 0; y < Ht; y++) c[y] = y < SH ? (int)tmp[y * LS + j] : 0;
         if (wht) {
             if constexpr (TX == 0) {
-                iwht4(c);
 #pragma unroll
-                for (int y = 0; y < 4; y++) colres[y] = c[y];
+                for (int y = 0; y < 4; y++) c[y] = wt[y * 4 + j];   // (not the slab read above)
+                iwht4(c);
+                // the column result does not fit int16 either (131068 above). Saturating is
+                // exact: any |r| > 32767 exceeds bdmax, and the pixel clips to the same bound
+#pragma unroll
+                for (int y = 0; y < 4; y++) colres[y] = clampi(c[y], -32768, 32767);
             }
         } else {
             itx1d<Wide, Ht>(k_col_kind[b.txtp], c, col_lo, col_hi);
@@ -498,7 +511,7 @@ template <typename Px, typename Cf, typename Lt, bool Wide>
                              // spills, 27.8 us; 6: 80 + 220 B, 32.2; 4: 27.6-27.8; r06_itx_waves.txt)
 #endif
 __global__ __launch_bounds__(kItxThreads, MI_ITX_MIN_WAVES) void itx_frame_kernel(ItxArgs a) {
-    __shared__ Lt lds[itx_lds_max(true) > itx_lds_max(false) ? itx_lds_max(true) : itx_lds_max(false)];
+    __shared__ __attribute__((aligned(16))) Lt lds[itx_lds_max(true) > itx_lds_max(false) ? itx_lds_max(true) : itx_lds_max(false)];
     KTL(0);
     const int wg = blockIdx.x;
     // the size range holding this workgroup, with compile-time indices only (a runtime index

@@ -43,18 +43,27 @@ _LAYOUT = ("COUNT", "MUT_COUNT", "LF_NCELL", "LF_CELL_SIZE", "LF_NBR", "LF_NCMP"
            "LF", "CDEF_TIES", "CDEF_WIN", "CDEF_WIN_SUBTIE", "CDEF_VAR0", "CDEF_PX_BOTH", "CDEF_PX_CLAMPED",
            "CDEF_PX_SENTINEL", "CDEF_PX_PRISHIFT0", "CDEF_PX_NEG", "CDEF_PX_OUT0", "CDEF_PX_OUTMAX",
            "WIENER_HCLIP_LO", "WIENER_HCLIP_HI", "WIENER_VCLIP_LO", "WIENER_VCLIP_HI", "SGR_Z0", "SGR_Z255",
-           "SGR_PS31", "SGR_XSUM31", "SGR_OUT_LO", "SGR_OUT_HI", "LR_SET", "LR_WIENER")
+           "SGR_PS31", "SGR_XSUM31", "SGR_OUT_LO", "SGR_OUT_HI", "LR_SET", "LR_WIENER",
+           "ITX_ROW_CLIP_LO", "ITX_ROW_CLIP_HI", "ITX_COL_CLIP_LO", "ITX_COL_CLIP_HI", "ITX_MID_CLIP_LO",
+           "ITX_MID_CLIP_HI", "ITX_PX_CLIP_0", "ITX_PX_CLIP_MAX", "ITX_RES_GT_I16", "ITX_WHT_MID_GT_I16",
+           "ITX_ROT_GE_2P31", "MUT_ITX_ROT_I32", "MUT_ITX_NO_CLIP", "MUT_ITX_NO_MIDCLIP", "MUT_ITX_MID_I16",
+           "MUT_ITX_RES_I16", "MUT_ITX_WHT_MID_I16")
 
 
 class Census:
-    """The census flavour of the three in-loop filter restatements (oracle/census.h): the same
-    sources as liboracle.so with event counters and single-decision mutants. Its state is
-    global, so use it from one thread. Pass `.lib` as `lib=` to deblock_frame, cdef_frame and
-    lr_frame below."""
+    """The census flavour of the in-loop filter and inverse-transform restatements
+    (oracle/census.h): the same sources as liboracle.so with event counters and single-decision
+    mutants. Its state is global, so use it from one thread. Pass `.lib` as `lib=` to
+    deblock_frame, cdef_frame, lr_frame and itx_frame below."""
 
     def __init__(self, lib):
         self.lib = lib
         lib.oracle_census_read.argtypes = [_VP, ctypes.c_int]
+        lib.oracle_itxfm_add.argtypes = [ctypes.c_int, ctypes.c_int, _VP, ctypes.c_ssize_t, _VP, ctypes.c_int,
+                                         ctypes.c_int]
+        lib.oracle_itxfm_add.restype = None
+        lib.oracle_itx_frame.argtypes = [_VP, _VP, _VP, ctypes.c_int, _VP, ctypes.c_int]
+        lib.oracle_itx_frame.restype = None
         self.at = {n: lib.oracle_census_layout(i) for i, n in enumerate(_LAYOUT)}
         assert lib.oracle_census_layout(len(_LAYOUT)) == -1
 
@@ -68,6 +77,10 @@ class Census:
         out = np.zeros(self.at["COUNT"], np.uint64)
         self.lib.oracle_census_read(ptr(out), len(out))
         return out.astype(np.int64)
+
+    def itx(self, counts, name, bpc):
+        """One inverse-transform counter (name without the ITX_ prefix) of one bit depth."""
+        return int(counts[self.at["ITX_" + name] + (bpc - 8) // 2])
 
     def lf_cells(self, counts):
         """The deblock counters as [dir][cls][width index 4/6/8/16][LF_CELL_SIZE]."""
@@ -94,9 +107,9 @@ def itx_1d(kind, n, vec, lo=-(1 << 20), hi=(1 << 20) - 1):
     return c
 
 
-def itx_frame(planes, blocks, coef, bpc):
+def itx_frame(planes, blocks, coef, bpc, lib=None):
     """Run the oracle over numpy planes (list of 2-D arrays, modified in place) and arena."""
-    o = load_oracle()
+    o = lib or load_oracle()
     arrs = [np.ascontiguousarray(p) for p in planes]
     while len(arrs) < 3:
         arrs.append(arrs[0])
