@@ -181,7 +181,9 @@ int mi_display_tensor(MiCtx *ctx, const MiPicture *in, const MiTensorImage *out,
  *     caller has to choose, as for mtrx 2) and reserved values are -EINVAL, every other defined
  *     value (4, 8, 10, 11, 22) -ENOTSUP;
  *   trc 1, 6, 14, 15 (the BT.709 curve), 13 (sRGB), 16 (PQ, ST 2084); 2 and reserved values are
- *     -EINVAL, every other defined value (4, 5, 7 - 12, 17, 18: HLG among them) -ENOTSUP.
+ *     -EINVAL, every other defined value (4, 5, 7 - 12, 17, 18) -ENOTSUP. 18 (HLG, ARIB STD-B67)
+ *     is a source on a context that has opted in (mi_ctx_enable_hlg, "HLG sources" below) and
+ *     -ENOTSUP everywhere else.
  * Ms = 2^src_bpc - 1, Md = 2^dst_bpc - 1. Three tables, built on the host in double precision and
  * rounded once:
  *   lut_in[v], v = 0 .. Ms, x = v / Ms: linear light in [0, 1] as float32.
@@ -212,8 +214,9 @@ typedef struct MiToneMap {
     int32_t dst_pri;    /* Dav1dColorPrimaries of the output: 1 (BT.709), 9 (BT.2020), 12 (P3-D65) */
     int32_t dst_trc;    /* output OETF: 1 (BT.709) or 13 (sRGB) */
     int32_t dst_bpc;    /* output depth: 8, 10 or 12, independent of the source depth */
-    float src_peak;     /* PQ sources: mastering peak Lw, nits */
-    float dst_peak;     /* PQ sources: target peak Lmax, nits; linear light is normalised by it */
+    float src_peak;     /* PQ sources: mastering peak Lw, nits (HLG sources: not read) */
+    float dst_peak;     /* PQ sources: target peak Lmax, nits; linear light is normalised by it
+                           (HLG sources: the nominal peak of the display the OOTF renders for) */
 } MiToneMap;
 
 /* Host only, no device and no context: the tables the device stage uses for a source of
@@ -244,6 +247,60 @@ int mi_display_picture_tm(MiCtx *ctx, const MiPicture *in, const MiDisplayImage 
 int mi_display_tensor_tm(MiCtx *ctx, const MiPicture *in, const MiTensorImage *out,
                          const MiColorInfo *color, const MiToneMap *tm,
                          const MiFilmGrainData *fg, void *stream);
+
+/* ---- HLG sources (librav1d_amd.so) -------------------------------------------------------- */
+
+/* color->trc == 18 (HLG, BT.2100) as a source of the colour-volume stage, with any color->pri the
+ * stage converts (the pri rules are unchanged). A context accepts it only after
+ * mi_ctx_enable_hlg(ctx, 1): the flag is off in a new context, may be switched at any time between
+ * calls, and a context with it off (and a NULL `ctx`) answers trc 18 with -ENOTSUP exactly as
+ * before, so a caller that takes that answer as "convert it yourself" keeps getting it. Reading the
+ * flag of a non-NULL `ctx` is part of the checks: they still all precede device work, and the NULL
+ * `ctx` is still reported last. With the flag on, mi_display_picture_tm, mi_display_tensor_tm,
+ * mi_display_tensor_rs, mi_display_yuv_tm and mi_display_scaled_tm accept trc 18; they are defined
+ * through the picture P of mi_display_picture_tm as for every other source. -EINVAL for NULL `ctx`,
+ * else 0.
+ *
+ * The destination is as above (dst_pri, dst_trc, dst_bpc). tm->dst_peak is the nominal peak Lw of
+ * the display the picture is rendered for, finite and in [1, 10000], else -EINVAL. tm->src_peak is
+ * not read (any value, NaN included): HLG is scene-referred, and a dimmer display is served by the
+ * signal's own OOTF at that display's peak, so there is no EETF and no black lift (beta = 0).
+ *
+ * Tables, built on the host in double precision and rounded once:
+ *   lut_in[v], v = 0 .. Ms, x = v / Ms: the scene-linear signal, the HLG inverse OETF
+ *     E = x^2 / 3 for x <= 1/2, else min((exp((x - c) / a) + b) / 12, 1), a = 0.17883277,
+ *     b = 1 - 4a, c = 0.5 - a ln(4a), under the rules of lut_in above (entry 0 exactly 0, the
+ *     running maximum, a subnormal float32 becomes 0). It depends on the source depth alone.
+ *   yw[3]: the float32 of the Y row of RGB->XYZ of color->pri (BT.2020: 0.2627, 0.6780, 0.0593;
+ *     BT.2100 defines HLG on BT.2020, a stream with other primaries gets their own row).
+ *   lut_gain[1538]: the OOTF gain Y^(gamma - 1), gamma = 1.2 * 1.111^log2(Lw / 1000) (BT.2100-2
+ *     note 5, the extended range; 1.2 at 1000 nits). With U0 = 103 << 23 (the float32 bits of
+ *     2^-24) and U1 = 127 << 23 (of 1.0), y_k is the float32 of bit pattern min(U0 + (k << 17), U1)
+ *     and lut_gain[k] = float32(y_k^(gamma - 1)), k = 0 .. 1537: 64 nodes per octave over 24
+ *     octaves, entries 1536 and 1537 both exactly 1.
+ *   m[9] and lut_out are as above.
+ * Per pixel on the device, every float32 operation rounded separately (no fused multiply-add):
+ *   r = lut_in[R'], g = lut_in[G'], b = lut_in[B'];
+ *   Y = fl(fl(fl(yw[0] r) + fl(yw[1] g)) + fl(yw[2] b));
+ *   u = the bits of Y as an unsigned integer clamped to [U0, U1], d = u - U0, k = d >> 17,
+ *   f = float(d & 0x1FFFF) * 2^-17 (both exact);
+ *   gain = fl(lut_gain[k] + fl(f * fl(lut_gain[k + 1] - lut_gain[k])));
+ *   r = fl(r * gain), g = fl(g * gain), b = fl(b * gain);
+ *   then the rows of m, the clamp to [0, 1] (which also takes a channel that a gamma below 1 pushes
+ *   above 1) and lut_out as above. Node and fraction are integer operations on the bits of Y: the
+ *   device evaluates no transcendental, and the gain is linear in Y between nodes (within 2.8e-5
+ *   relative of Y^(gamma - 1) at dst_peak 1, below 1e-5 from dst_peak 50; half a 12-bit code is
+ *   1.2e-4). */
+int mi_ctx_enable_hlg(MiCtx *ctx, int on);
+
+/* Host only, no device and no context: mi_tonemap_tables for an HLG source, with the two tables it
+ * adds (yw 3 floats, lut_gain 1538). The argument rules of mi_tonemap_tables apply; -EINVAL also
+ * for a NULL yw or lut_gain, for a color->trc other than 18 and for a dst_peak that is not finite
+ * or lies outside [1, 10000]. (mi_tonemap_tables itself has no context and keeps answering trc 18
+ * with -ENOTSUP.) */
+int mi_tonemap_tables_hlg(const MiToneMap *tm, const MiColorInfo *color, int src_bpc,
+                          float *lut_in, float m[9], uint16_t *lut_out, float yw[3],
+                          float *lut_gain /* 1538 */);
 
 /* ---- scaled semi-planar output (librav1d_amd.so) ------------------------------------------ */
 

@@ -246,6 +246,11 @@ def lib():
                                                 ctypes.POINTER(MiFilmGrainData), _VP])
     _sig(L, "mi_display_scaled_tm", ctypes.c_int, [_VP, ctypes.POINTER(MiPicture), _VP, ctypes.c_int, _VP, _VP, _VP, _VP,
                                                    ctypes.POINTER(MiFilmGrainData), _VP])
+    # HLG sources (a library from before them, loaded with MI_LIB by the A/B tools, lacks the two:
+    # the wrappers in rav1d_amd/display.py then raise AttributeError, nothing stands in)
+    if hasattr(L, "mi_ctx_enable_hlg"):
+        _sig(L, "mi_ctx_enable_hlg", ctypes.c_int, [_VP, ctypes.c_int])
+        _sig(L, "mi_tonemap_tables_hlg", ctypes.c_int, [_VP, _VP, ctypes.c_int, _VP, _VP, _VP, _VP, _VP])
     # (mi_picture_light_level, its variant entry and mi_light_level_stats get their signatures in
     # rav1d_amd/display.py on first use, so that tools/light_bench.py --peaks-only can load a
     # library from before them with MI_LIB)
@@ -268,7 +273,7 @@ EXPORTED = ["mi_version", "mi_ctx_create", "mi_ctx_destroy", "mi_ctx_last_error"
             "mi_host_picture_alloc", "mi_host_picture_free", "mi_output_picture", "mi_display_picture",
             "mi_display_tensor", "mi_tonemap_tables", "mi_display_picture_tm", "mi_display_tensor_tm",
             "mi_display_scaled", "mi_display_tensor_rs", "mi_display_scaled_rs", "mi_resample_plan", "mi_resample_taps",
-            "mi_display_yuv_tm", "mi_display_scaled_tm",
+            "mi_display_yuv_tm", "mi_display_scaled_tm", "mi_ctx_enable_hlg", "mi_tonemap_tables_hlg",
             "mi_picture_light_level", "mi_picture_light_level_variant", "mi_light_level_stats"]
 
 

@@ -518,12 +518,24 @@ struct ToneArgs {
     int n_in;                     // 1 << source bpc
     int maxd;                     // 2^dst_bpc - 1: alpha
 };
+// HLG sources (trc 18): between lut_in and the matrix the OOTF gain of the pixel's luminance,
+// Y = yw . (r, g, b), read from lut_gain by the bits of Y (64 nodes per octave over 2^-24 .. 1,
+// linear between nodes). What tone_prepare hands the launchers: lut_gain is nullptr for every other
+// source, and the kernels of those take the ToneArgs part alone.
+constexpr int kToneGain = 1538;   // entries of lut_gain
+struct ToneHlgArgs : ToneArgs {
+    const float *lut_gain;        // kToneGain entries
+    float yw[3];                  // the Y row of RGB -> XYZ of the source primaries
+};
 struct NoTone {};
-template <bool TM> struct ToneSel { using type = NoTone; };
-template <> struct ToneSel<true> { using type = ToneArgs; };
-template <bool TM> using ToneParam = typename ToneSel<TM>::type;
+// the stage of a kernel: none, the table stage, the table stage with the HLG gain
+enum { kToneNone = 0, kToneTable = 1, kToneHlg = 2 };
+template <int TM> struct ToneSel { using type = NoTone; };
+template <> struct ToneSel<kToneTable> { using type = ToneArgs; };
+template <> struct ToneSel<kToneHlg> { using type = ToneHlgArgs; };
+template <int TM> using ToneParam = typename ToneSel<TM>::type;
 // RGB formats only; the destination samples are u8 at dst_bpc 8, else u16
-int launch_display_tm(const DisplayArgs &a, const ToneArgs &tm, int bpc, int dst_bpc, int format, hipStream_t s);
+int launch_display_tm(const DisplayArgs &a, const ToneHlgArgs &tm, int bpc, int dst_bpc, int format, hipStream_t s);
 
 // tone-mapped YUV output (yuv_tm.hip): after the colour-volume stage the forward matrix to the
 // target's Y'CbCr (14-bit fixed point, include/mi_av1out.h "the picture Q") and the chroma
@@ -536,7 +548,7 @@ struct YuvArgs {
     int shift;                    // interleaved store: 16 - d for d > 8, else 0
 };
 // planar: the scratch picture (samples LSB-aligned, u8 at dst_bpc 8, else u16); else semi-planar
-int launch_yuv_tm(const DisplayArgs &a, const ToneArgs &tm, const YuvArgs &f, int bpc, int dst_bpc, bool planar, hipStream_t s);
+int launch_yuv_tm(const DisplayArgs &a, const ToneHlgArgs &tm, const YuvArgs &f, int bpc, int dst_bpc, bool planar, hipStream_t s);
 
 // the separable resize of the tensor and scaled outputs (resize.h): one axis of a tap table, and
 // the list of axes one launch of the taps kernel fills (a scaled call: up to 8 rungs of luma x,
@@ -571,7 +583,7 @@ enum { kTensorCHW = 0, kTensorHWC = 1, kTensorAny = 2 };
 // the two passes (the tap tables are in place); tm: the colour-volume stage in the tile fill of
 // the horizontal pass, or nullptr; cubic: the tables hold signed taps (MI_RS_CUBIC) and the passes
 // clamp their sums to [0, (256 << shift) - 1]
-int launch_tensor(const TensorArgs &t, int bpc, int order, hipStream_t s, const ToneArgs *tm = nullptr, bool cubic = false);
+int launch_tensor(const TensorArgs &t, int bpc, int order, hipStream_t s, const ToneHlgArgs *tm = nullptr, bool cubic = false);
 
 // scaled semi-planar output (scaled.hip): per rung, the luma plane and the U / V pair each cropped,
 // resized (resize.h, with the chroma siting in the taps), converted to the rung's depth and stored

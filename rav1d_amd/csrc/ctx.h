@@ -78,7 +78,9 @@ struct MiCtx {
     // the peaks zeroed for sources that do not read them, pri, trc, source bpc), their matrix, and
     // two pinned staging buffers used in turn; `tone_ev[i]` marks when buffer i may be rewritten.
     // tone_prepare compares the key per table (lut_out: dst_trc, dst_bpc; lut_in: peaks, trc,
-    // source bpc; m: the primaries) and rebuilds only the stale ones
+    // source bpc; m: the primaries) and rebuilds only the stale ones. HLG sources (accepted only
+    // with `hlg` set: mi_ctx_enable_hlg): lut_gain behind lut_in with a key of its own (the bits
+    // of dst_peak), and the luminance row `tone_yw`, built with m
     uint8_t *tone_dev = nullptr;
     uint8_t *tone_host[2] = {nullptr, nullptr};
     hipEvent_t tone_ev[2] = {nullptr, nullptr};
@@ -87,6 +89,10 @@ struct MiCtx {
     bool tone_valid = false;
     int32_t tone_key[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     float tone_m[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    bool hlg = false;
+    bool tone_gain_valid = false;
+    int32_t tone_gain_key = 0;
+    float tone_yw[3] = {0, 0, 0};
     // persistent intra reconstruction: per-block done epochs, queue heads, error word
     uint32_t *ir_done = nullptr;
     size_t ir_done_n = 0;

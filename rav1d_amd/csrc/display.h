@@ -7,6 +7,8 @@
 // upsampler, the matrix, the colour-volume stage), so both compute the same picture. The resize of
 // the tensor and scaled outputs is resize.h.
 #pragma once
+#include <type_traits>
+
 #include "mi_av1out.h"
 #include "ctx.h"
 
@@ -44,26 +46,28 @@ void display_source(const MiPicture &src, const MiColorInfo *color, DisplayArgs 
 
 // ---- host (tonemap.cpp) ----
 // The rules of the colour-volume stage for `tm` and the source description in `color` (not NULL):
-// 0, -EINVAL or -ENOTSUP as include/mi_av1out.h lists them. No device work.
-int tone_check(const MiToneMap *tm, const MiColorInfo *color);
+// 0, -EINVAL or -ENOTSUP as include/mi_av1out.h lists them; `hlg`: trc 18 is a source (the flag of
+// the context, mi_ctx_enable_hlg; false without one). No device work.
+int tone_check(const MiToneMap *tm, const MiColorInfo *color, bool hlg);
 // The context's device tables for (tm, color, src_bpc), all checked before: built and uploaded on
 // `s` when they differ from the ones it holds. 0, -ENOMEM or -EIO (with last_error set).
-int tone_prepare(MiCtx *ctx, const MiToneMap *tm, const MiColorInfo *color, int src_bpc, hipStream_t s, ToneArgs &t);
+// t.lut_gain is nullptr unless the source is HLG.
+int tone_prepare(MiCtx *ctx, const MiToneMap *tm, const MiColorInfo *color, int src_bpc, hipStream_t s, ToneHlgArgs &t);
 
 // ---- host (yuv_tm.hip) ----
 // The rules of the tone-mapped YUV outputs beyond their plain entries': -EINVAL for NULL `tm` or
 // `target`, the colour rules of the RGB formats (display_color) and of the stage (tone_check), then
 // -EINVAL for a target matrix that is no Kr / Kb matrix or a range that is not 0 / 1; else 0 with
-// the inverse matrix in `a` and the forward coefficients in `f`. No device work.
+// the inverse matrix in `a` and the forward coefficients in `f`; `hlg` as for tone_check. No device work.
 int yuv_tm_check(const MiPicture *in, const MiColorInfo *color, const MiToneMap *tm, const MiYuvTarget *target,
-                 DisplayArgs &a, YuvArgs &f);
+                 bool hlg, DisplayArgs &a, YuvArgs &f);
 // The context's scratch picture for Q of `in` at dst_bpc in *q (planar, 128-byte aligned rows),
 // allocated or grown: 0 or -ENOMEM (with last_error set). Nothing launched.
 int yuv_tm_scratch(MiCtx *ctx, const MiPicture *in, int dst_bpc, MiPicture *q);
 // Enqueue Q of `src` (the source, grained where the call has grain) on `s`: into the planes of `q`
 // (planar) or into dst[0] = Y and dst[1] = interleaved UV with the strides given (q NULL). `a` and
 // `f` from yuv_tm_check, `tm` from tone_prepare. 0 or -1.
-int yuv_tm_picture(const MiPicture &src, const MiColorInfo *color, DisplayArgs a, const ToneArgs &tm, const YuvArgs &f,
+int yuv_tm_picture(const MiPicture &src, const MiColorInfo *color, DisplayArgs a, const ToneHlgArgs &tm, const YuvArgs &f,
                    const MiPicture *q, void *const dst[2], const ptrdiff_t dstride[2], int dst_bpc, hipStream_t s);
 
 // ---- device ----
@@ -79,17 +83,60 @@ __device__ __forceinline__ void tone_stage(const ToneArgs &tm, float *lds, int t
         *reinterpret_cast<float4 *>(lds + i) = *reinterpret_cast<const float4 *>(tm.lut_in + i);
 }
 
+// The HLG stage (Tone = ToneHlgArgs) reads lut_gain (6152 B) from the workgroup's copy in LDS too,
+// behind lut_in in one array; kHlgGainLds false reads it from global memory like lut_out (the switch
+// the two were timed with: DESIGN.md, HLG sources: from LDS the HLG calls take 0.92 - 0.98 of the
+// time they take with lut_gain in global memory, 4K10).
+#ifndef MI_HLG_GAIN_GLOBAL
+constexpr bool kHlgGainLds = true;
+#else
+constexpr bool kHlgGainLds = false;
+#endif
+constexpr int kToneGainPad = (kToneGain + 3) & ~3;   // whole float4s: the device table is padded to it
+// floats of the workgroup's table array
+template <typename Tone> constexpr int tone_lds() {
+    return kToneIn + (std::is_same_v<Tone, ToneHlgArgs> && kHlgGainLds ? kToneGainPad : 0);
+}
+// the HLG workgroup's copy of lut_gain at lds + kToneIn: every thread calls it, before the barrier
+__device__ __forceinline__ void tone_stage(const ToneHlgArgs &tm, float *lds, int tid, int nthreads) {
+    tone_stage(static_cast<const ToneArgs &>(tm), lds, tid, nthreads);
+    if constexpr (kHlgGainLds)
+        for (int i = 4 * tid; i < kToneGainPad; i += 4 * nthreads)
+            *reinterpret_cast<float4 *>(lds + kToneIn + i) = *reinterpret_cast<const float4 *>(tm.lut_gain + i);
+}
+
+constexpr uint32_t kGainU0 = 103u << 23, kGainU1 = 127u << 23;   // the bits of 2^-24 and of 1.0
+
 // 8 pixels of source-coded R'G'B' to destination-coded R'G'B', in place; `lin` is the workgroup's
-// copy of lut_in. Every float32 operation is rounded on its own: the pragma keeps the compiler from
-// contracting the products and sums into fused multiply-adds (as scale_bias in tensor.hip).
-__device__ __forceinline__ void tone_run(const ToneArgs &tm, const float *lin, int (&R)[8], int (&G)[8], int (&B)[8]) {
+// copy of lut_in (and, for HLG, of lut_gain behind it). Every float32 operation is rounded on its
+// own: the pragma keeps the compiler from contracting the products and sums into fused
+// multiply-adds (as scale_bias in tensor.hip).
+template <typename Tone>
+__device__ __forceinline__ void tone_run(const Tone &tm, const float *lin, int (&R)[8], int (&G)[8], int (&B)[8]) {
 #pragma clang fp contract(off)
 #pragma unroll
     for (int k = 0; k < 8; k++) {
         // (the matrix clips to [0, Ms]; the identity hands samples on, which a valid picture
         // keeps in that range: the min holds the index inside the table whatever the planes hold)
         const int top = tm.n_in - 1;
-        const float r = lin[min(R[k], top)], g = lin[min(G[k], top)], b = lin[min(B[k], top)];
+        float r = lin[min(R[k], top)], g = lin[min(G[k], top)], b = lin[min(B[k], top)];
+        if constexpr (std::is_same_v<Tone, ToneHlgArgs>) {
+            // the OOTF gain of the luminance: node and fraction are the bits of Y (a negative or
+            // tiny Y clamps to node 0, Y above 1 to the last node, whose neighbour is entry 1537)
+            const float y0 = tm.yw[0] * r, y1 = tm.yw[1] * g, y2 = tm.yw[2] * b;
+            const float ys = y0 + y1;
+            const float Y = ys + y2;
+            const uint32_t u = min(max(__float_as_uint(Y), kGainU0), kGainU1), d = u - kGainU0;
+            const float *gt = kHlgGainLds ? lin + kToneIn : tm.lut_gain;
+            const float g0 = gt[d >> 17], g1 = gt[(d >> 17) + 1];
+            const float f = (float)(d & 0x1ffffu) * 0x1p-17f;
+            const float dg = g1 - g0;
+            const float fd = f * dg;
+            const float gain = g0 + fd;
+            r = r * gain;
+            g = g * gain;
+            b = b * gain;
+        }
         int o[3];
 #pragma unroll
         for (int c = 0; c < 3; c++) {

@@ -16,7 +16,8 @@
 // mi_display_picture_tm is the same kernel with the colour-volume stage (display.h tone_run: two
 // table gathers per channel around a 3 x 3 float32 matrix) between the matrix and the store, a
 // compile-time switch; its destination samples have the type of dst_bpc, not the source's. The
-// instantiations without the stage are the code they were before it existed.
+// instantiations without the stage are the code they were before it existed, and those with it the
+// code they were before the third mode, HLG sources (the OOTF gain between lut_in and the matrix).
 #include <cerrno>
 #include <cmath>
 #include <cstring>
@@ -28,7 +29,7 @@ namespace {
 
 // 8 pixels of luma row `row` to R'G'B' samples of type Px (the destination's: the source's own
 // type, or with the colour-volume stage TM the type of dst_bpc)
-template <typename Px, int FMT, bool TM>
+template <typename Px, int FMT, int TM>
 __device__ __forceinline__ void rgb_row(const DisplayArgs &a, const ToneParam<TM> &tm, const float *lin, int row, int x0,
                                         const int (&y)[8], const int (&cu)[8], const int (&cv)[8]) {
     int R[8], G[8], B[8];
@@ -92,12 +93,12 @@ __device__ __forceinline__ void rgb_row(const DisplayArgs &a, const ToneParam<TM
 }
 
 // Px: the source samples; Dx: the destination samples (Px unless TM); TM: the colour-volume
-// stage after the matrix (RGB formats)
-template <typename Px, typename Dx, int FMT, bool TM>
+// stage after the matrix (RGB formats): kToneNone, kToneTable, or kToneHlg with the HLG gain
+template <typename Px, typename Dx, int FMT, int TM>
 __global__ __launch_bounds__(256) void display_kernel(const DisplayArgs a, const ToneParam<TM> tm) {
     [[maybe_unused]] const float *lin = nullptr;
     if constexpr (TM) {   // (before any lane leaves: every lane fills the table and meets the barrier)
-        __shared__ __attribute__((aligned(16))) float lut[kToneIn];
+        __shared__ __attribute__((aligned(16))) float lut[tone_lds<ToneParam<TM>>()];
         tone_stage(tm, lut, threadIdx.y * 64 + threadIdx.x, 256);
         __syncthreads();
         lin = lut;
@@ -164,21 +165,28 @@ template <typename Px>
 int launch_px(const DisplayArgs &a, int format, hipStream_t s) {
     const dim3 block(64, 4), grid((a.chunks + 63) / 64, (a.units + 3) / 4);
     switch (format) {
-    case MI_OUT_SEMIPLANAR: display_kernel<Px, Px, MI_OUT_SEMIPLANAR, false><<<grid, block, 0, s>>>(a, NoTone()); break;
-    case MI_OUT_RGB_PLANAR: display_kernel<Px, Px, MI_OUT_RGB_PLANAR, false><<<grid, block, 0, s>>>(a, NoTone()); break;
-    default: display_kernel<Px, Px, MI_OUT_RGBA_PACKED, false><<<grid, block, 0, s>>>(a, NoTone()); break;
+    case MI_OUT_SEMIPLANAR: display_kernel<Px, Px, MI_OUT_SEMIPLANAR, kToneNone><<<grid, block, 0, s>>>(a, NoTone()); break;
+    case MI_OUT_RGB_PLANAR: display_kernel<Px, Px, MI_OUT_RGB_PLANAR, kToneNone><<<grid, block, 0, s>>>(a, NoTone()); break;
+    default: display_kernel<Px, Px, MI_OUT_RGBA_PACKED, kToneNone><<<grid, block, 0, s>>>(a, NoTone()); break;
     }
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-template <typename Px, typename Dx>
-int launch_tm(const DisplayArgs &a, const ToneArgs &tm, int format, hipStream_t s) {
+template <typename Px, typename Dx, int TM>
+int launch_tm(const DisplayArgs &a, const ToneParam<TM> &tm, int format, hipStream_t s) {
     const dim3 block(64, 4), grid((a.chunks + 63) / 64, (a.units + 3) / 4);
     if (format == MI_OUT_RGB_PLANAR)
-        display_kernel<Px, Dx, MI_OUT_RGB_PLANAR, true><<<grid, block, 0, s>>>(a, tm);
+        display_kernel<Px, Dx, MI_OUT_RGB_PLANAR, TM><<<grid, block, 0, s>>>(a, tm);
     else
-        display_kernel<Px, Dx, MI_OUT_RGBA_PACKED, true><<<grid, block, 0, s>>>(a, tm);
+        display_kernel<Px, Dx, MI_OUT_RGBA_PACKED, TM><<<grid, block, 0, s>>>(a, tm);
     return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+template <int TM>
+int launch_tm_px(const DisplayArgs &a, const ToneParam<TM> &tm, int bpc, int dst_bpc, int format, hipStream_t s) {
+    if (bpc == 8)
+        return dst_bpc == 8 ? launch_tm<uint8_t, uint8_t, TM>(a, tm, format, s) : launch_tm<uint8_t, uint16_t, TM>(a, tm, format, s);
+    return dst_bpc == 8 ? launch_tm<uint16_t, uint8_t, TM>(a, tm, format, s) : launch_tm<uint16_t, uint16_t, TM>(a, tm, format, s);
 }
 
 }  // namespace
@@ -187,10 +195,9 @@ int launch_display(const DisplayArgs &a, int bpc, int format, hipStream_t s) {
     return bpc == 8 ? launch_px<uint8_t>(a, format, s) : launch_px<uint16_t>(a, format, s);
 }
 
-int launch_display_tm(const DisplayArgs &a, const ToneArgs &tm, int bpc, int dst_bpc, int format, hipStream_t s) {
-    if (bpc == 8)
-        return dst_bpc == 8 ? launch_tm<uint8_t, uint8_t>(a, tm, format, s) : launch_tm<uint8_t, uint16_t>(a, tm, format, s);
-    return dst_bpc == 8 ? launch_tm<uint16_t, uint8_t>(a, tm, format, s) : launch_tm<uint16_t, uint16_t>(a, tm, format, s);
+int launch_display_tm(const DisplayArgs &a, const ToneHlgArgs &tm, int bpc, int dst_bpc, int format, hipStream_t s) {
+    return tm.lut_gain ? launch_tm_px<kToneHlg>(a, tm, bpc, dst_bpc, format, s)
+                       : launch_tm_px<kToneTable>(a, tm, bpc, dst_bpc, format, s);
 }
 
 
@@ -330,13 +337,13 @@ int display_picture(MiCtx *ctx, const MiPicture *in, const MiDisplayImage *out, 
     if (out->format != MI_OUT_SEMIPLANAR)
         if (int e = mi::display_color(in, color, a)) return e;
     if (tone) {
-        if (int e = mi::tone_check(tm, color)) return e;
+        if (int e = mi::tone_check(tm, color, ctx && ctx->hlg)) return e;
         if (out->bpc != tm->dst_bpc) return -EINVAL;
     }
     if (!ctx) return -EINVAL;
 
     // allocations and the table upload first: a call that fails there has launched nothing
-    mi::ToneArgs ta;
+    mi::ToneHlgArgs ta;
     if (tone)
         if (int e = mi::tone_prepare(ctx, tm, color, in->bpc, (hipStream_t)stream, ta)) return e;
     MiPicture src = *in;

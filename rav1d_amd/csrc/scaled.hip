@@ -246,7 +246,7 @@ int display_scaled(MiCtx *ctx, const MiPicture *in, const MiScaledImage *outs, i
     memset(&ya, 0, sizeof(ya));
     memset(&yf, 0, sizeof(yf));
     if (yt)
-        if (int e = mi::yuv_tm_check(in, color, yt->tm, yt->target, ya, yf)) return e;
+        if (int e = mi::yuv_tm_check(in, color, yt->tm, yt->target, ctx && ctx->hlg, ya, yf)) return e;
     if (!ctx) return -EINVAL;
 
     // the scratch: every rung's tables (they stay while the axes stay), then one `mid` the rungs
@@ -284,7 +284,7 @@ int display_scaled(MiCtx *ctx, const MiPicture *in, const MiScaledImage *outs, i
         }
     mi::tap_filter(tl, flt);
     const bool taps = !sc.holds(tl);
-    mi::ToneArgs ta;
+    mi::ToneHlgArgs ta;
     MiPicture q;
     if (yt) {
         if (int e = mi::yuv_tm_scratch(ctx, in, yt->tm->dst_bpc, &q)) return e;

@@ -21,7 +21,8 @@
 //                        destination's order, as whole vectors where the pointer and strides allow.
 //
 // mi_display_tensor_tm: the colour-volume stage (display.h tone_run) runs in the tile fill of
-// tensor_h_kernel, a compile-time switch, so the passes resize the tone-mapped picture at dst_bpc.
+// tensor_h_kernel, a compile-time switch (none, the table stage, the table stage with the HLG gain),
+// so the passes resize the tone-mapped picture at dst_bpc.
 // A cubic's taps are signed: CUBIC, a compile-time switch of both passes, clamps what the shift
 // gives to [0, M]; the triangle's instantiations are the code they were without it.
 #include <algorithm>
@@ -38,7 +39,7 @@ namespace {
 
 // 8 pixels of one row to R'G'B' (with TM: through the colour-volume stage, to samples of dst_bpc),
 // one 16-byte LDS write per channel at column `col` of the tile
-template <bool TM>
+template <int TM>
 __device__ __forceinline__ void tile_row(const DisplayArgs &a, const ToneParam<TM> &tm, const float *lin, const int (&y)[8],
                                          const int (&cu)[8], const int (&cv)[8], uint16_t (&tile)[3][kTensorSeg], int col) {
     int R[8], G[8], B[8];
@@ -50,12 +51,12 @@ __device__ __forceinline__ void tile_row(const DisplayArgs &a, const ToneParam<T
 }
 
 // ---- horizontal pass ----
-template <typename Px, bool TM, bool CUBIC>
+template <typename Px, int TM, bool CUBIC>
 __global__ __launch_bounds__(256) void tensor_h_kernel(const TensorArgs t, const ToneParam<TM> tm) {
     __shared__ __attribute__((aligned(16))) uint16_t tile[2][3][kTensorSeg];
     [[maybe_unused]] const float *lin = nullptr;
     if constexpr (TM) {
-        __shared__ __attribute__((aligned(16))) float lut[kToneIn];
+        __shared__ __attribute__((aligned(16))) float lut[tone_lds<ToneParam<TM>>()];
         tone_stage(tm, lut, threadIdx.x, 256);
         __syncthreads();
         lin = lut;
@@ -222,17 +223,22 @@ void launch_v(const TensorArgs &t, int order, dim3 grid, hipStream_t s) {
 }
 
 template <bool CUBIC>
-int launch_passes(const TensorArgs &t, int bpc, int order, hipStream_t s, const ToneArgs *tm) {
+int launch_passes(const TensorArgs &t, int bpc, int order, hipStream_t s, const ToneHlgArgs *tm) {
     const dim3 hgrid(t.units, t.segs);
-    if (tm) {
+    if (tm && tm->lut_gain) {
         if (bpc == 8)
-            tensor_h_kernel<uint8_t, true, CUBIC><<<hgrid, 256, 0, s>>>(t, *tm);
+            tensor_h_kernel<uint8_t, kToneHlg, CUBIC><<<hgrid, 256, 0, s>>>(t, *tm);
         else
-            tensor_h_kernel<uint16_t, true, CUBIC><<<hgrid, 256, 0, s>>>(t, *tm);
+            tensor_h_kernel<uint16_t, kToneHlg, CUBIC><<<hgrid, 256, 0, s>>>(t, *tm);
+    } else if (tm) {
+        if (bpc == 8)
+            tensor_h_kernel<uint8_t, kToneTable, CUBIC><<<hgrid, 256, 0, s>>>(t, *tm);
+        else
+            tensor_h_kernel<uint16_t, kToneTable, CUBIC><<<hgrid, 256, 0, s>>>(t, *tm);
     } else if (bpc == 8) {
-        tensor_h_kernel<uint8_t, false, CUBIC><<<hgrid, 256, 0, s>>>(t, NoTone());
+        tensor_h_kernel<uint8_t, kToneNone, CUBIC><<<hgrid, 256, 0, s>>>(t, NoTone());
     } else {
-        tensor_h_kernel<uint16_t, false, CUBIC><<<hgrid, 256, 0, s>>>(t, NoTone());
+        tensor_h_kernel<uint16_t, kToneNone, CUBIC><<<hgrid, 256, 0, s>>>(t, NoTone());
     }
     if (hipGetLastError() != hipSuccess) return -1;
     const dim3 vgrid((unsigned)t.xblocks * (unsigned)t.oh);
@@ -247,7 +253,7 @@ int launch_passes(const TensorArgs &t, int bpc, int order, hipStream_t s, const 
 
 }  // namespace
 
-int launch_tensor(const TensorArgs &t, int bpc, int order, hipStream_t s, const ToneArgs *tm, bool cubic) {
+int launch_tensor(const TensorArgs &t, int bpc, int order, hipStream_t s, const ToneHlgArgs *tm, bool cubic) {
     return cubic ? launch_passes<true>(t, bpc, order, s, tm) : launch_passes<false>(t, bpc, order, s, tm);
 }
 
@@ -285,7 +291,7 @@ int display_tensor(MiCtx *ctx, const MiPicture *in, const MiTensorImage *out, co
     memset(&t, 0, sizeof(t));
     if (int e = mi::display_color(in, color, t.d)) return e;
     if (tone)
-        if (int e = mi::tone_check(tm, color)) return e;
+        if (int e = mi::tone_check(tm, color, ctx && ctx->hlg)) return e;
     if (!ctx) return -EINVAL;
 
     // geometry of the passes and of the scratch
@@ -314,7 +320,7 @@ int display_tensor(MiCtx *ctx, const MiPicture *in, const MiTensorImage *out, co
     tl.ax[tl.n++] = mi::TapAxis{ch, oh, 2, t.tv, t.tab + (int64_t)(t.th + 2) * ow};
     mi::tap_filter(tl, flt);
     const bool taps = !sc.holds(tl);
-    mi::ToneArgs ta;
+    mi::ToneHlgArgs ta;
     if (tone)
         if (int e = mi::tone_prepare(ctx, tm, color, in->bpc, (hipStream_t)stream, ta)) return e;
     MiPicture src = *in;

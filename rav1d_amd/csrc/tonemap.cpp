@@ -1,7 +1,9 @@
 // tonemap.cpp — the host side of the colour-volume stage (include/mi_av1out.h, MiToneMap): the
-// rules, the three tables in double precision (mi_tonemap_tables), and the context's device copy
+// rules, the three tables in double precision (mi_tonemap_tables), for HLG sources the luminance
+// row and the OOTF gain table beside them (mi_tonemap_tables_hlg), and the context's device copy
 // of them, rebuilt and uploaded on the caller's stream only when the description changes. The
-// device side is tone_run (display.h), inside display_kernel and tensor_h_kernel.
+// device side is tone_run (display.h), inside display_kernel, tensor_h_kernel and yuv_tm_kernel.
+#include <algorithm>
 #include <cerrno>
 #include <cmath>
 #include <cstring>
@@ -22,15 +24,17 @@ int pri_class(int pri) {
     }
 }
 
-enum { kCurve709 = 0, kCurveSrgb = 1, kCurvePq = 2 };
+enum { kCurve709 = 0, kCurveSrgb = 1, kCurvePq = 2, kCurveHlg = 3 };
 
-// the curve of a source trc in *curve, or -ENOTSUP (defined) or -EINVAL (2, reserved)
-int trc_class(int trc, int *curve) {
+// the curve of a source trc in *curve, or -ENOTSUP (defined; HLG unless `hlg`) or -EINVAL (2,
+// reserved)
+int trc_class(int trc, int *curve, bool hlg) {
     switch (trc) {
     case 1: case 6: case 14: case 15: *curve = kCurve709; return 0;
     case 13: *curve = kCurveSrgb; return 0;
     case 16: *curve = kCurvePq; return 0;
-    case 4: case 5: case 7: case 8: case 9: case 10: case 11: case 12: case 17: case 18: return -ENOTSUP;
+    case 18: *curve = kCurveHlg; return hlg ? 0 : -ENOTSUP;
+    case 4: case 5: case 7: case 8: case 9: case 10: case 11: case 12: case 17: return -ENOTSUP;
     default: return -EINVAL;
     }
 }
@@ -51,10 +55,20 @@ double pq_eotf(double e) {
     return 10000.0 * pow(fmax(p - kC1, 0.0) / (kC2 - kC3 * p), 1.0 / kM1);
 }
 
+// ---- ARIB STD-B67 (HLG) ----
+constexpr double kHlgA = 0.17883277, kHlgB = 1.0 - 4.0 * kHlgA;
+
+// the inverse OETF: the scene-linear signal in [0, 1] of x in [0, 1]
+double hlg_inv_oetf(double x) {
+    const double c = 0.5 - kHlgA * log(4.0 * kHlgA);
+    return x <= 0.5 ? x * x / 3.0 : fmin((exp((x - c) / kHlgA) + kHlgB) / 12.0, 1.0);
+}
+
 // linear light in [0, 1] of source code value x in [0, 1]
 double linear_of(int curve, double x, double src_peak, double dst_peak) {
     if (curve == kCurve709) return x < 0.081 ? x / 4.5 : pow((x + 0.099) / 1.099, 1.0 / 0.45);
     if (curve == kCurveSrgb) return x <= 0.04045 ? x / 12.92 : pow((x + 0.055) / 1.055, 2.4);
+    if (curve == kCurveHlg) return hlg_inv_oetf(x);
     // PQ through the BT.2390 EETF (black level 0)
     const double ns = pq_inv_eotf(src_peak), nd = pq_inv_eotf(dst_peak);
     const double e1 = fmin(x / ns, 1.0), max_lum = fmin(nd / ns, 1.0), ks = 1.5 * max_lum - 0.5;
@@ -116,7 +130,7 @@ void invert3(const double (&a)[3][3], double (&o)[3][3]) {
 // the three tables, each from what it depends on alone; every argument checked before
 void tone_table_in(const MiToneMap &tm, int trc, int src_bpc, float *lut_in) {
     int curve = kCurve709;
-    (void)trc_class(trc, &curve);
+    (void)trc_class(trc, &curve, true);
     const int n = 1 << src_bpc;
     const double ms = (double)(n - 1);
     // (the running maximum: the BT.709 curve's two segments, with the constants as rounded in the
@@ -147,6 +161,27 @@ void tone_table_out(int dst_trc, int dst_bpc, uint16_t *lut_out) {
     for (int i = 0; i < kOutN; i++) lut_out[i] = (uint16_t)floor(oetf(dst_trc, (double)i / 65535.0) * md + 0.5);
 }
 
+// HLG: the Y row of RGB -> XYZ of the source primaries
+void tone_table_yw(int pri, float *yw) {
+    double s[3][3];
+    rgb_to_xyz(pri, s);
+    for (int c = 0; c < 3; c++) yw[c] = (float)s[1][c];
+}
+
+// HLG: the OOTF gain Y^(gamma - 1) at the nodes of lut_gain, gamma = 1.2 * 1.111^log2(Lw / 1000)
+// (BT.2100-2 note 5, the extended range). Node k is the float32 of bit pattern
+// min(U0 + (k << 17), U1), U0 = 2^-24 and U1 = 1.0: entries 1536 and 1537 are exactly 1.
+void tone_table_gain(float dst_peak, float *lut_gain) {
+    const double gamma = 1.2 * pow(1.111, log2((double)dst_peak / 1000.0));
+    const uint32_t u0 = 103u << 23, u1 = 127u << 23;
+    for (int k = 0; k < kToneGain; k++) {
+        const uint32_t u = std::min(u0 + ((uint32_t)k << 17), u1);
+        float y;
+        memcpy(&y, &u, sizeof(y));
+        lut_gain[k] = (float)pow((double)y, gamma - 1.0);
+    }
+}
+
 void tone_tables(const MiToneMap &tm, int pri, int trc, int src_bpc, float *lut_in, float *m, uint16_t *lut_out) {
     tone_table_in(tm, trc, src_bpc, lut_in);
     tone_table_m(tm.dst_pri, pri, m);
@@ -155,32 +190,39 @@ void tone_tables(const MiToneMap &tm, int pri, int trc, int src_bpc, float *lut_
 
 }  // namespace
 
-int tone_check(const MiToneMap *tm, const MiColorInfo *color) {
+int tone_check(const MiToneMap *tm, const MiColorInfo *color, bool hlg) {
     if (!tm || !color) return -EINVAL;
     if (tm->dst_pri != 1 && tm->dst_pri != 9 && tm->dst_pri != 12) return -EINVAL;
     if (tm->dst_trc != 1 && tm->dst_trc != 13) return -EINVAL;
     if (tm->dst_bpc != 8 && tm->dst_bpc != 10 && tm->dst_bpc != 12) return -EINVAL;
     // -EINVAL of either field before -ENOTSUP of the other: a malformed description is reported as such
     int curve = kCurve709;
-    const int pe = pri_class(color->pri), te = trc_class(color->trc, &curve);
+    const int pe = pri_class(color->pri), te = trc_class(color->trc, &curve, hlg);
     if (pe == -EINVAL || te == -EINVAL) return -EINVAL;
     if (pe || te) return -ENOTSUP;
     if (curve == kCurvePq && (!peak_ok(tm->src_peak) || !peak_ok(tm->dst_peak))) return -EINVAL;
+    // (HLG is scene-referred: dst_peak is the display the OOTF renders for, src_peak is not read)
+    if (curve == kCurveHlg && !peak_ok(tm->dst_peak)) return -EINVAL;
     return 0;
 }
 
-int tone_prepare(MiCtx *ctx, const MiToneMap *tm, const MiColorInfo *color, int src_bpc, hipStream_t s, ToneArgs &t) {
+int tone_prepare(MiCtx *ctx, const MiToneMap *tm, const MiColorInfo *color, int src_bpc, hipStream_t s, ToneHlgArgs &t) {
     int curve = kCurve709;
-    (void)trc_class(color->trc, &curve);
-    // the key: what the tables depend on (sources other than PQ do not read the peaks)
+    (void)trc_class(color->trc, &curve, true);
+    const bool hlg = curve == kCurveHlg;
+    // the key: what the tables depend on (sources other than PQ do not read the peaks: the
+    // dst_peak of an HLG source is the key of lut_gain alone)
     MiToneMap k = *tm;
     if (curve != kCurvePq) k.src_peak = k.dst_peak = 0.0f;
+    int32_t gain_key = 0;
+    memcpy(&gain_key, &tm->dst_peak, sizeof(float));
     int32_t key[8] = {k.dst_pri, k.dst_trc, k.dst_bpc, 0, 0, color->pri, color->trc, src_bpc};
     memcpy(&key[3], &k.src_peak, sizeof(float));
     memcpy(&key[4], &k.dst_peak, sizeof(float));
     const size_t out_bytes = (size_t)kOutN * sizeof(uint16_t), in_bytes = (size_t)kToneIn * sizeof(float);
+    const size_t gain_bytes = (size_t)kToneGainPad * sizeof(float);   // (behind lut_in, padded to whole float4s)
     if (!ctx->tone_dev) {
-        if (hipMalloc(&ctx->tone_dev, out_bytes + in_bytes) != hipSuccess) {
+        if (hipMalloc(&ctx->tone_dev, out_bytes + in_bytes + gain_bytes) != hipSuccess) {
             ctx->tone_dev = nullptr;
             return ctx->last_error = -ENOMEM;
         }
@@ -192,13 +234,16 @@ int tone_prepare(MiCtx *ctx, const MiToneMap *tm, const MiColorInfo *color, int 
     const bool out_stale = !ctx->tone_valid || key[1] != old[1] || key[2] != old[2];
     const bool in_stale = !ctx->tone_valid || key[3] != old[3] || key[4] != old[4] || key[6] != old[6] || key[7] != old[7];
     const bool m_stale = !ctx->tone_valid || key[0] != old[0] || key[5] != old[5];
-    if (out_stale || in_stale) {
+    // lut_gain is HLG's alone and keyed on its own: PQ and SDR calls in between leave it in place,
+    // and a change of dst_peak rebuilds its 1538 entries and neither of the big tables
+    const bool gain_stale = hlg && (!ctx->tone_gain_valid || gain_key != ctx->tone_gain_key);
+    if (out_stale || in_stale || gain_stale) {
         // Build into the staging buffer whose turn it is. The upload before the last one read it;
         // wait for that one only if it is still pending (two buffers: a change of tables behind
         // another does not wait for the stream).
         const int i = ctx->tone_slot;
         if (!ctx->tone_host[i]) {
-            if (hipHostMalloc((void **)&ctx->tone_host[i], out_bytes + in_bytes, hipHostMallocDefault) != hipSuccess) {
+            if (hipHostMalloc((void **)&ctx->tone_host[i], out_bytes + in_bytes + gain_bytes, hipHostMallocDefault) != hipSuccess) {
                 ctx->tone_host[i] = nullptr;
                 return ctx->last_error = -ENOMEM;
             }
@@ -212,14 +257,26 @@ int tone_prepare(MiCtx *ctx, const MiToneMap *tm, const MiColorInfo *color, int 
             ctx->tone_ev_pending[i] = false;
         }
         uint8_t *h = ctx->tone_host[i];
-        ctx->tone_valid = false;
-        if (out_stale) tone_table_out(k.dst_trc, k.dst_bpc, (uint16_t *)h);
-        if (in_stale) tone_table_in(k, color->trc, src_bpc, (float *)(h + out_bytes));
-        // (the tables are adjacent, on the host as on the device: one copy of what changed)
-        const size_t from = out_stale ? 0 : out_bytes;
-        const size_t to = in_stale ? out_bytes + ((size_t)sizeof(float) << src_bpc) : out_bytes;
-        if (hipMemcpyAsync(ctx->tone_dev + from, h + from, to - from, hipMemcpyHostToDevice, s) != hipSuccess)
-            return ctx->last_error = -EIO;
+        if (out_stale || in_stale) {
+            ctx->tone_valid = false;
+            if (out_stale) tone_table_out(k.dst_trc, k.dst_bpc, (uint16_t *)h);
+            if (in_stale) tone_table_in(k, color->trc, src_bpc, (float *)(h + out_bytes));
+            // (the tables are adjacent, on the host as on the device: one copy of what changed)
+            const size_t from = out_stale ? 0 : out_bytes;
+            const size_t to = in_stale ? out_bytes + ((size_t)sizeof(float) << src_bpc) : out_bytes;
+            if (hipMemcpyAsync(ctx->tone_dev + from, h + from, to - from, hipMemcpyHostToDevice, s) != hipSuccess)
+                return ctx->last_error = -EIO;
+        }
+        if (gain_stale) {
+            ctx->tone_gain_valid = false;
+            float *g = (float *)(h + out_bytes + in_bytes);
+            tone_table_gain(tm->dst_peak, g);
+            for (int j = kToneGain; j < kToneGainPad; j++) g[j] = 1.0f;
+            if (hipMemcpyAsync(ctx->tone_dev + out_bytes + in_bytes, g, gain_bytes, hipMemcpyHostToDevice, s) != hipSuccess)
+                return ctx->last_error = -EIO;
+            ctx->tone_gain_key = gain_key;
+            ctx->tone_gain_valid = true;
+        }
         if (hipEventRecord(ctx->tone_ev[i], s) != hipSuccess) {
             // without the event the buffer's reuse cannot be ordered: let the upload finish now
             (void)hipStreamSynchronize(s);
@@ -228,7 +285,10 @@ int tone_prepare(MiCtx *ctx, const MiToneMap *tm, const MiColorInfo *color, int 
         }
         ctx->tone_slot = i ^ 1;
     }
-    if (m_stale) tone_table_m(k.dst_pri, color->pri, ctx->tone_m);
+    if (m_stale) {
+        tone_table_m(k.dst_pri, color->pri, ctx->tone_m);
+        tone_table_yw(color->pri, ctx->tone_yw);
+    }
     memcpy(ctx->tone_key, key, sizeof(key));
     ctx->tone_valid = true;
     t.lut_out = (const uint16_t *)ctx->tone_dev;
@@ -236,6 +296,8 @@ int tone_prepare(MiCtx *ctx, const MiToneMap *tm, const MiColorInfo *color, int 
     memcpy(t.m, ctx->tone_m, sizeof(t.m));
     t.n_in = 1 << src_bpc;
     t.maxd = (1 << tm->dst_bpc) - 1;
+    t.lut_gain = hlg ? (const float *)(ctx->tone_dev + out_bytes + in_bytes) : nullptr;
+    memcpy(t.yw, ctx->tone_yw, sizeof(t.yw));
     return 0;
 }
 
@@ -244,8 +306,25 @@ int tone_prepare(MiCtx *ctx, const MiToneMap *tm, const MiColorInfo *color, int 
 extern "C" int mi_tonemap_tables(const MiToneMap *tm, const MiColorInfo *color, int src_bpc, float *lut_in, float m[9],
                                  uint16_t *lut_out) {
     if (!lut_in || !m || !lut_out || (src_bpc != 8 && src_bpc != 10 && src_bpc != 12)) return -EINVAL;
-    if (int e = mi::tone_check(tm, color)) return e;
+    if (int e = mi::tone_check(tm, color, false)) return e;
     mi::tone_tables(*tm, color->pri, color->trc, src_bpc, lut_in, m, lut_out);
+    return 0;
+}
+
+extern "C" int mi_tonemap_tables_hlg(const MiToneMap *tm, const MiColorInfo *color, int src_bpc, float *lut_in, float m[9],
+                                     uint16_t *lut_out, float yw[3], float *lut_gain) {
+    if (!lut_in || !m || !lut_out || !yw || !lut_gain || (src_bpc != 8 && src_bpc != 10 && src_bpc != 12)) return -EINVAL;
+    if (!tm || !color || color->trc != 18) return -EINVAL;
+    if (int e = mi::tone_check(tm, color, true)) return e;
+    mi::tone_tables(*tm, color->pri, color->trc, src_bpc, lut_in, m, lut_out);
+    mi::tone_table_yw(color->pri, yw);
+    mi::tone_table_gain(tm->dst_peak, lut_gain);
+    return 0;
+}
+
+extern "C" int mi_ctx_enable_hlg(MiCtx *ctx, int on) {
+    if (!ctx) return -EINVAL;
+    ctx->hlg = on != 0;
     return 0;
 }
 

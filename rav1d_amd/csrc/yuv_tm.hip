@@ -34,7 +34,8 @@ constexpr int kYuvChunks = 63;   // the chunks a wave stores: lanes 1 .. 63
 
 // 8 pixels of a luma row (luma, chroma at luma resolution) to tone-mapped R'G'B' as the RGB
 // formats of mi_display_picture_tm compute it, then the forward matrix: Y, U4, V4
-__device__ __forceinline__ void forward_run(const DisplayArgs &a, const ToneArgs &tm, const YuvArgs &f, const float *lin,
+template <typename Tone>
+__device__ __forceinline__ void forward_run(const DisplayArgs &a, const Tone &tm, const YuvArgs &f, const float *lin,
                                             const int (&y)[8], const int (&cu)[8], const int (&cv)[8], int (&Y)[8],
                                             int (&U)[8], int (&V)[8]) {
     int R[8], G[8], B[8];
@@ -88,10 +89,11 @@ __device__ __forceinline__ void store_uv(const DisplayArgs &a, const YuvArgs &f,
 }
 
 // Px: the source samples; Dx: the destination samples (of dst_bpc); PLANAR: the scratch picture
-// (LSB-aligned planes), else semi-planar (MSB-aligned, interleaved UV)
-template <typename Px, typename Dx, bool PLANAR>
-__global__ __launch_bounds__(256) void yuv_tm_kernel(const DisplayArgs a, const ToneArgs tm, const YuvArgs f) {
-    __shared__ __attribute__((aligned(16))) float lut[kToneIn];
+// (LSB-aligned planes), else semi-planar (MSB-aligned, interleaved UV); TM: kToneTable, or kToneHlg
+// with the HLG gain in the stage
+template <typename Px, typename Dx, bool PLANAR, int TM>
+__global__ __launch_bounds__(256) void yuv_tm_kernel(const DisplayArgs a, const ToneParam<TM> tm, const YuvArgs f) {
+    __shared__ __attribute__((aligned(16))) float lut[tone_lds<ToneParam<TM>>()];
     __shared__ uint4 above[4][64][2];   // a wave's odd row: U4, V4 as 8 u16 each
     tone_stage(tm, lut, threadIdx.y * 64 + threadIdx.x, 256);
     __syncthreads();
@@ -206,29 +208,35 @@ __global__ __launch_bounds__(256) void yuv_tm_kernel(const DisplayArgs a, const 
     if (active) store_uv<Dx, PLANAR, 4>(a, f, u, x0 >> 1, su, sv);
 }
 
-template <typename Px, typename Dx>
-int launch_px(const DisplayArgs &a, const ToneArgs &tm, const YuvArgs &f, bool planar, hipStream_t s) {
+template <typename Px, typename Dx, int TM>
+int launch_px(const DisplayArgs &a, const ToneParam<TM> &tm, const YuvArgs &f, bool planar, hipStream_t s) {
     const dim3 block(64, 4), grid((a.chunks + kYuvChunks - 1) / kYuvChunks, (a.units + 3) / 4);
     if (planar)
-        yuv_tm_kernel<Px, Dx, true><<<grid, block, 0, s>>>(a, tm, f);
+        yuv_tm_kernel<Px, Dx, true, TM><<<grid, block, 0, s>>>(a, tm, f);
     else
-        yuv_tm_kernel<Px, Dx, false><<<grid, block, 0, s>>>(a, tm, f);
+        yuv_tm_kernel<Px, Dx, false, TM><<<grid, block, 0, s>>>(a, tm, f);
     return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+template <int TM>
+int launch_tm(const DisplayArgs &a, const ToneParam<TM> &tm, const YuvArgs &f, int bpc, int dst_bpc, bool planar, hipStream_t s) {
+    if (bpc == 8)
+        return dst_bpc == 8 ? launch_px<uint8_t, uint8_t, TM>(a, tm, f, planar, s) : launch_px<uint8_t, uint16_t, TM>(a, tm, f, planar, s);
+    return dst_bpc == 8 ? launch_px<uint16_t, uint8_t, TM>(a, tm, f, planar, s) : launch_px<uint16_t, uint16_t, TM>(a, tm, f, planar, s);
 }
 
 }  // namespace
 
-int launch_yuv_tm(const DisplayArgs &a, const ToneArgs &tm, const YuvArgs &f, int bpc, int dst_bpc, bool planar, hipStream_t s) {
-    if (bpc == 8)
-        return dst_bpc == 8 ? launch_px<uint8_t, uint8_t>(a, tm, f, planar, s) : launch_px<uint8_t, uint16_t>(a, tm, f, planar, s);
-    return dst_bpc == 8 ? launch_px<uint16_t, uint8_t>(a, tm, f, planar, s) : launch_px<uint16_t, uint16_t>(a, tm, f, planar, s);
+int launch_yuv_tm(const DisplayArgs &a, const ToneHlgArgs &tm, const YuvArgs &f, int bpc, int dst_bpc, bool planar, hipStream_t s) {
+    return tm.lut_gain ? launch_tm<kToneHlg>(a, tm, f, bpc, dst_bpc, planar, s)
+                       : launch_tm<kToneTable>(a, tm, f, bpc, dst_bpc, planar, s);
 }
 
 int yuv_tm_check(const MiPicture *in, const MiColorInfo *color, const MiToneMap *tm, const MiYuvTarget *target,
-                 DisplayArgs &a, YuvArgs &f) {
+                 bool hlg, DisplayArgs &a, YuvArgs &f) {
     if (!tm || !target) return -EINVAL;
     if (int e = display_color(in, color, a)) return e;
-    if (int e = tone_check(tm, color)) return e;
+    if (int e = tone_check(tm, color, hlg)) return e;
     double kr, kb;
     // (the caller chooses the target: a value without a Kr / Kb matrix is malformed, not unsupported)
     if (matrix_k(target->mtrx, &kr, &kb) || (target->range != 0 && target->range != 1)) return -EINVAL;
@@ -276,7 +284,7 @@ int yuv_tm_scratch(MiCtx *ctx, const MiPicture *in, int dst_bpc, MiPicture *q) {
     return 0;
 }
 
-int yuv_tm_picture(const MiPicture &src, const MiColorInfo *color, DisplayArgs a, const ToneArgs &tm, const YuvArgs &f,
+int yuv_tm_picture(const MiPicture &src, const MiColorInfo *color, DisplayArgs a, const ToneHlgArgs &tm, const YuvArgs &f,
                    const MiPicture *q, void *const dst[2], const ptrdiff_t dstride[2], int dst_bpc, hipStream_t s) {
     display_source(src, color, a);
     const int ndst = src.layout ? (q ? 3 : 2) : 1;
@@ -314,12 +322,12 @@ extern "C" int mi_display_yuv_tm(MiCtx *ctx, const MiPicture *in, const MiDispla
     mi::YuvArgs f;
     memset(&a, 0, sizeof(a));
     memset(&f, 0, sizeof(f));
-    if (int e = mi::yuv_tm_check(in, color, tm, target, a, f)) return e;
+    if (int e = mi::yuv_tm_check(in, color, tm, target, ctx && ctx->hlg, a, f)) return e;
     if (out->bpc != tm->dst_bpc) return -EINVAL;
     if (!ctx) return -EINVAL;
 
     // allocations and the table upload first: a call that fails there has launched nothing
-    mi::ToneArgs ta;
+    mi::ToneHlgArgs ta;
     if (int e = mi::tone_prepare(ctx, tm, color, in->bpc, (hipStream_t)stream, ta)) return e;
     MiPicture src = *in;
     if (fg)

@@ -98,7 +98,8 @@ class MiToneMap(ctypes.Structure):
 def ToneMap(dst_pri=1, dst_trc=13, dst_bpc=8, src_peak=1000.0, dst_peak=100.0):
     """A MiToneMap: the output's primaries (1 BT.709, 9 BT.2020, 12 P3-D65), OETF (1 BT.709,
     13 sRGB) and depth (8, 10, 12), and for PQ sources the mastering and the target peak in nits.
-    The defaults take HDR10 to 8-bit sRGB at 100 nits."""
+    For HLG sources (enable_hlg) dst_peak is the nominal peak of the display the picture is rendered
+    for and src_peak is not read. The defaults take HDR10 to 8-bit sRGB at 100 nits."""
     return MiToneMap(int(dst_pri), int(dst_trc), int(dst_bpc), float(src_peak), float(dst_peak))
 
 
@@ -114,6 +115,35 @@ def tonemap_tables(tm, color, src_bpc):
                                   lut_in.ctypes.data_as(ctypes.c_void_p), m.ctypes.data_as(ctypes.c_void_p),
                                   lut_out.ctypes.data_as(ctypes.c_void_p)), "mi_tonemap_tables")
     return lut_in, m.reshape(3, 3), lut_out
+
+
+GAIN_NODES = 1538   # entries of lut_gain
+
+
+def enable_hlg(ctx, on=True):
+    """mi_ctx_enable_hlg: let `ctx` take HLG sources (color.trc 18) in display_picture,
+    display_tensor, display_yuv and display_scaled with a ToneMap, whose dst_peak is then the
+    nominal peak of the display the picture is rendered for (src_peak is not read). Off in a new
+    context; a context with it off answers trc 18 with ENOTSUP. Raises MiError on a negative
+    return."""
+    check(lib().mi_ctx_enable_hlg(ctx.h if ctx is not None else None, 1 if on else 0), "mi_ctx_enable_hlg")
+
+
+def tonemap_tables_hlg(tm, color, src_bpc):
+    """mi_tonemap_tables_hlg (host only): (lut_in float32 [1 << src_bpc], m float32 [3, 3],
+    lut_out uint16 [65536], yw float32 [3], lut_gain float32 [1538]), the tables the device stage
+    uses for an HLG source (color.trc 18) of `src_bpc` bits with the primaries color.pri, rendered
+    for a display of tm.dst_peak nits. Raises MiError on a negative return."""
+    lut_in = np.empty(1 << src_bpc if src_bpc in (8, 10, 12) else 1, dtype=np.float32)
+    m = np.empty(9, dtype=np.float32)
+    lut_out = np.empty(65536, dtype=np.uint16)
+    yw = np.empty(3, dtype=np.float32)
+    lut_gain = np.empty(GAIN_NODES, dtype=np.float32)
+    check(lib().mi_tonemap_tables_hlg(ctypes.byref(tm) if tm is not None else None,
+                                      ctypes.byref(color) if color is not None else None, int(src_bpc),
+                                      *(a.ctypes.data_as(ctypes.c_void_p) for a in (lut_in, m, lut_out, yw, lut_gain))),
+          "mi_tonemap_tables_hlg")
+    return lut_in, m.reshape(3, 3), lut_out, yw, lut_gain
 
 
 def _source_args(frame, color, fg):
@@ -462,6 +492,6 @@ __all__ = ["DisplayImage", "MiDisplayImage", "MiColorInfo", "display_picture", "
            "MiScaledImage", "ScaledImage", "display_scaled", "even_crop",
            "OUT_SEMIPLANAR", "OUT_RGB_PLANAR", "OUT_RGBA_PACKED",
            "MiTensorImage", "tensor_image", "display_tensor", "T_U8", "T_F16", "T_BF16", "T_F32",
-           "MiToneMap", "ToneMap", "tonemap_tables", "MiYuvTarget", "YuvTarget", "display_yuv", "output_colour",
+           "MiToneMap", "ToneMap", "tonemap_tables", "enable_hlg", "tonemap_tables_hlg", "MiYuvTarget", "YuvTarget", "display_yuv", "output_colour",
            "MiLightLevel", "light_level", "light_stats",
            "MiResample", "Resample", "RESAMPLE_PRESETS", "RS_TRIANGLE", "RS_CUBIC", "resample_plan", "resample_taps"]

@@ -212,10 +212,15 @@ def decode_to_tensors(ctx, data, format="nv12", apply_grain=True, matrix=None, s
     the image holds samples of tonemap.dst_bpc bits in the tone map's primaries and transfer.
     primaries, transfer: Dav1dColorPrimaries / Dav1dTransferCharacteristics values that override
     the stream's (as matrix does; the MiColorInfo yielded carries them). With tonemap, a stream
-    that leaves either unspecified and has no override raises ValueError.
+    that leaves either unspecified and has no override raises ValueError. An HLG source (trc 18,
+    the stream's or transfer=18) is taken only by a context the caller has opted in with
+    rav1d_amd.display.enable_hlg(ctx): the helpers of this module never switch it on themselves, and
+    on any other context the call raises MiError (ENOTSUP), as it always did. tonemap.dst_peak is
+    then the peak of the display the picture is rendered for, and src_peak is not read.
 
     peak: where a PQ source's src_peak comes from (read with tonemap only, and for a source whose
-    trc after the overrides is 16: a ValueError otherwise when it is not None). None: the tone
+    trc after the overrides is 16: a ValueError otherwise when it is not None, HLG included, which
+    reads no src_peak for the modes to choose). None: the tone
     map's own. "metadata": per shown picture, the stream's mastering display or content light
     (metadata_peak). "measured": per shown picture, the 99.99th percentile of max(R', G', B') of
     the picture itself (rav1d_amd.display.light_level, without grain) through a PeakTracker; this
@@ -263,7 +268,8 @@ def decode_to_batches(ctx, data, size, batch=8, dtype=None, channels_last=False,
     stream each get their own crop), resized, normalised with mean / std per channel, with film
     grain when the frame carries it and apply_grain is set. The list holds the colour description
     used for each slot; matrix, tonemap, primaries and transfer follow decode_to_tensors's rules
-    (with tonemap the slot is mi_display_tensor_tm's: the tone-mapped picture, resized). resample: a
+    (with tonemap the slot is mi_display_tensor_tm's: the tone-mapped picture, resized; an HLG
+    source needs a context the caller has opted in with rav1d_amd.display.enable_hlg). resample: a
     MiResample (rav1d_amd.display.Resample, "catmull_rom" for models trained on bicubic-resized
     inputs): the filter of the resize, None the triangle. peak: decode_to_tensors's, per picture that
     is output (a skipped picture is not measured). Each tensor is a fresh allocation
@@ -320,7 +326,8 @@ def decode_to_ladder(ctx, data, sizes, bpc=None, fit="stretch", apply_grain=True
     (rav1d_amd.display.output_colour gives the tags of the rungs). primaries, transfer, matrix: the
     overrides of decode_to_tensors, by its rules: with tonemap, a stream that leaves primaries or
     transfer unspecified and has no override raises ValueError before any device work of the
-    picture. Without tonemap the overrides are not read and nothing changes (a target on its own is a
+    picture, and an HLG source (trc 18) needs a context the caller has opted in with
+    rav1d_amd.display.enable_hlg (this helper never does; peak stays a ValueError for it). Without tonemap the overrides are not read and nothing changes (a target on its own is a
     ValueError: there is no matrix or range conversion without a tone map). peak: decode_to_tensors's:
     where a PQ source's src_peak comes from, per shown picture. Every tensor is
     a fresh allocation the caller owns, filled by work enqueued on `stream` (synchronise it, or

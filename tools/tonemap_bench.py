@@ -27,6 +27,20 @@ the existing call it stands beside, into profiles/yuv_tm_bench.json by default:
   ladder           plain mi_display_scaled, 1920 x 1080, 1280 x 720 and 640 x 360 in one call;
   ladder_tm        mi_display_scaled_tm, the same three rungs.
 
+With --hlg the run measures HLG sources (the same picture read as trc 18 on a context with
+rav1d_amd.display.enable_hlg, rendered for the tone map's dst_peak), each row between two takes of
+its PQ counterpart, into profiles/hlg_bench.json by default; the ratios HLG / PQ are recorded:
+
+  rgba8_hlg        mi_display_picture_tm beside rgba8_tm;
+  tensor_hlg       mi_display_tensor_tm beside tensor_tm;
+  nv12_hlg         mi_display_yuv_tm beside nv12_tm.
+
+--fold FILE... (with --hlg) folds earlier outputs of this tool into the document: runs of the
+existing rows on the library before a change and on the one after it, alternating in one session,
+told apart by --note ("parent#1", "change#1", "parent#2", ...). Per row it records every value, the
+spread the parent's runs show between themselves, and whether every run of the change lies within
+that spread of the parent's range.
+
 A variant build of the library (MI_BUILD_VARIANT of rav1d_amd/build.py, loaded with MI_LIB) is
 measured by the same command with another --out; --note says which it was.
 """
@@ -42,8 +56,12 @@ sys.path.insert(0, ROOT)
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=None, help="default: profiles/tonemap_bench.json, with --yuv profiles/yuv_tm_bench.json")
+    ap.add_argument("--out", default=None, help="default: profiles/tonemap_bench.json, with --yuv profiles/yuv_tm_bench.json, "
+                    "with --hlg profiles/hlg_bench.json")
     ap.add_argument("--yuv", action="store_true", help="measure the tone-mapped YUV outputs and their baselines")
+    ap.add_argument("--hlg", action="store_true", help="measure HLG sources, each row between two takes of its PQ counterpart")
+    ap.add_argument("--fold", nargs="*", default=[], metavar="FILE", help="with --hlg: earlier outputs of this tool (parent#n / "
+                    "change#n notes) to fold into the document")
     ap.add_argument("--width", type=int, default=3840)
     ap.add_argument("--height", type=int, default=2160)
     ap.add_argument("--bpc", type=int, default=10)
@@ -53,8 +71,11 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--note", default="")
     args = ap.parse_args()
+    if args.yuv and args.hlg:
+        sys.exit("--yuv and --hlg are two runs")
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "yuv_tm_bench.json" if args.yuv else "tonemap_bench.json")
+        name = "yuv_tm_bench.json" if args.yuv else "hlg_bench.json" if args.hlg else "tonemap_bench.json"
+        args.out = os.path.join(ROOT, "profiles", name)
 
     import numpy as np
     import torch
@@ -124,6 +145,8 @@ def main():
 
     if args.yuv:
         return yuv_rows(args, L, ctx, pic, color, tm8, sp, timed, entry, (w, h, bpc, layout))
+    if args.hlg:
+        return hlg_rows(args, L, ctx, pic, color, tm8, sp, timed, entry, (w, h, bpc, layout), cases, t_tm)
 
     results = {}
     order = ["rgba10", "rgba8_tm", "rgba10_tm", "rgba10", "tensor", "tensor_tm", "tensor"]
@@ -205,6 +228,83 @@ def yuv_rows(args, L, ctx, pic, color, tm8, sp, timed, entry, geom):
         f.write("\n")
     print(json.dumps({k: doc[k] for k in ("rgb8_tm_us", "scaled_1080_us", "ladder_us", "ratio_nv12_tm_to_rgb8_tm",
                                           "ratio_scaled_1080_tm_to_scaled_1080", "ratio_ladder_tm_to_ladder")}))
+    print("wrote", args.out)
+
+
+def fold(files):
+    """The runs of the existing rows in `files` (outputs of this tool), grouped by the note's name
+    before '#': per mode and row every value in microseconds, the spread of the parent's runs, the
+    difference of the means, and whether every run of the change lies within the parent's range
+    widened by that spread."""
+    runs = {}
+    for path in files:
+        with open(path) as f:
+            doc = json.load(f)
+        side = doc.get("note", "").split("#")[0]
+        for row, v in doc["results"].items():
+            runs.setdefault(doc["tool"], {}).setdefault(row, {}).setdefault(side, []).append(v["us"])
+    out = {}
+    for mode, rows in runs.items():
+        out[mode] = {}
+        for row, sides in rows.items():
+            rec = dict(sides)
+            parent, change = sides.get("parent", []), sides.get("change", [])
+            if len(parent) >= 2 and change:
+                spread = max(parent) - min(parent)
+                rec["parent_spread_us"] = round(spread, 2)
+                rec["change_minus_parent_us"] = round(sum(change) / len(change) - sum(parent) / len(parent), 2)
+                rec["within_parent_spread"] = all(min(parent) - spread <= c <= max(parent) + spread for c in change)
+            out[mode][row] = rec
+    return out
+
+
+def hlg_rows(args, L, ctx, pic, color, tm8, sp, timed, entry, geom, cases, t_tm):
+    """The --hlg run, on main's source picture, context and timer: the three HLG rows, each between
+    two takes of its PQ counterpart (main's rgba8_tm and tensor_tm, --yuv's nv12_tm)."""
+    import torch
+
+    from rav1d_amd import LIB_PATH
+    from rav1d_amd.display import DisplayImage, YuvTarget, enable_hlg
+    w, h, bpc, layout = geom
+    ref = ctypes.byref
+    enable_hlg(ctx)
+    hlg = type(color)(color.pri, 18, color.mtrx, color.range, color.chr)
+    target = YuvTarget(1, 0)
+    im8, nv12 = DisplayImage(w, h, bpc, layout, "rgba", out_bpc=8), DisplayImage(w, h, bpc, layout, "nv12", out_bpc=8)
+    d8, d_nv12 = im8.image(), nv12.image()
+    cases = dict(cases)
+    cases.update({
+        "rgba8_hlg": entry(L.mi_display_picture_tm, ctx.h, ref(pic), ref(d8), ref(hlg), ref(tm8), None, sp),
+        "tensor_hlg": entry(L.mi_display_tensor_tm, ctx.h, ref(pic), ref(t_tm), ref(hlg), ref(tm8), None, sp),
+        "nv12_tm": entry(L.mi_display_yuv_tm, ctx.h, ref(pic), ref(d_nv12), ref(color), ref(tm8), ref(target), None, sp),
+        "nv12_hlg": entry(L.mi_display_yuv_tm, ctx.h, ref(pic), ref(d_nv12), ref(hlg), ref(tm8), ref(target), None, sp),
+    })
+    results = {}
+    pairs = [("rgba8_tm", "rgba8_hlg"), ("tensor_tm", "tensor_hlg"), ("nv12_tm", "nv12_hlg")]
+    for pq, row in pairs:
+        for name in (pq, row, pq):
+            us, rounds = timed(cases[name])
+            key = name if name not in results else name + "_again"
+            results[key] = dict(us=round(us, 2), rounds_us=rounds)
+            print(json.dumps({key: results[key]}), flush=True)
+    doc = dict(tool="tools/tonemap_bench.py --hlg", device=torch.cuda.get_device_name(0), library=os.path.basename(LIB_PATH),
+               note=args.note, width=w, height=h, bpc=bpc, layout="4:2:0", out_w=args.size[0], out_h=args.size[1],
+               source="BT.2020 (pri 9, mtrx 9, limited, chr 0) read as PQ (trc 16) and as HLG (trc 18), uniformly random codes",
+               tonemap="to sRGB / BT.709 at 8 bits, src_peak 1000 (PQ only), dst_peak 100; NV12 target BT.709 limited",
+               iters=args.iters, warmup=args.warmup, rounds=args.rounds,
+               timing="HIP events around back-to-back calls; median of rounds; the PQ row before and after its HLG row",
+               results=results)
+    for pq, row in pairs:
+        base = (results[pq]["us"] + results[pq + "_again"]["us"]) / 2
+        doc[pq + "_us"] = round(base, 2)
+        doc[f"ratio_{row}_to_{pq}"] = round(results[row]["us"] / base, 3)
+    if args.fold:
+        doc["existing_rows"] = fold(args.fold)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(doc, f, indent=1)
+        f.write("\n")
+    print(json.dumps({k: v for k, v in doc.items() if k.startswith("ratio_")}))
     print("wrote", args.out)
 
 
